@@ -7,6 +7,12 @@ is one process per GPU with no data-path collective (replicas, "weak"); a
 gloo process group only provides the barrier and the max-over-ranks time.
 
     python bench.py [--gpus N --steps K --warmup W --batch 32 --preset r101vd --size 640]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up, W warmup steps, K timed steps, the
+outputs of the last timed step to DIR (--dump-outputs), the result line. Everything else the bench
+measures (HIP-event rooflines and the per-class breakdown, --detail, the CPU baseline, the
+host-input leg and the p50 latency) runs with --full only.
 
 --gpus N > 1 without a torch.distributed launcher: the parent process spawns N
 replica processes BEFORE any GPU call, each pinned to one device with
@@ -15,7 +21,7 @@ HIP_VISIBLE_DEVICES (one Serve replica per GPU); under
 cuda:LOCAL_RANK. Either way the ranks meet only in a gloo barrier and the max
 of their elapsed times; value = all ranks' images / that max.
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (the
+Prints ONE JSON line (rank 0) with the contract fields; with --full also `roofline` (the
 dominant kernel: the fp32-accurate 3-way-split implicit-GEMM conv, HIP-event
 timed inside the timed region, priced against ITS pipe ceiling: 2500/6 TFLOP/s
 fp32-equivalent on the bf16 MFMA) and `cpu_baseline` (the reference HF path on
@@ -48,6 +54,13 @@ def parse():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--preset", default="r101vd")
     ap.add_argument("--size", type=int, default=640)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (scores, labels, boxes, "
+                         "counts, logits, pred_boxes) as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: HIP-event rooflines and the per-class "
+                         "breakdown (--detail), the CPU baseline, the host-input leg and the p50 latency (each with "
+                         "its own --no-* / --latency-iters switch)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=4.0,
                     help="minimum duration of each timed bs1 CPU run (3 runs, median)")
     ap.add_argument("--cpu-baseline-batch", type=int, default=32,
@@ -80,7 +93,12 @@ def parse():
                     help="seconds the gloo rendezvous / barrier waits for a missing rank")
     ap.add_argument("--stub-step-ms", type=float, default=None, help=argparse.SUPPRESS)  # CPU launcher test
     ap.add_argument("--stub-fail-rank", type=int, default=None, help=argparse.SUPPRESS)  # CPU launcher test
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.detail and not args.full:
+        ap.error("--detail needs --full (the per-shape timings come from the profiling pass)")
+    return args
 
 
 # the C5 mixed-resolution stream: source (h, w) sizes cycled image by image
@@ -497,6 +515,7 @@ def make_step(args, rank, local):
     counts = torch.empty((B,), dtype=torch.int32, device=dev)
     work = torch.empty((B, K), dtype=torch.int32, device=dev)
     it = [0]
+    last = {}
 
     def step():
         imgs, tsz = batches[it[0] % len(batches)]
@@ -504,7 +523,15 @@ def make_step(args, rank, local):
         ops.preprocess_u8(imgs, px, S, S)
         logits, pred = eng.forward(px)
         ops.postprocess(logits, pred, tsz, K, 0.5, scores, labels, boxes, counts, work)
+        last["logits"], last["pred_boxes"] = logits, pred  # engine-owned, overwritten by the next forward
 
+    def outputs():
+        """What the last step returned, as host float32 arrays (--dump-outputs): the post-processed detections
+        (all K sorted candidates per image; the first counts[b] pass the threshold) and the forward's outputs."""
+        dev_out = dict(scores=scores, labels=labels, boxes=boxes, counts=counts, **last)
+        return {k: v.detach().to("cpu", torch.float32).numpy() for k, v in dev_out.items()}
+
+    step.outputs = outputs
     step.cfg, step.weights = cfg, weights
     step.input_supply = None
     if args.stream == "same":
@@ -567,6 +594,24 @@ def host_input_leg(torch, ops, eng, imgs_host, dev, px, tsz, outs, S, K, steps, 
                            "h2d_gbps": round(nbytes / up_ms / 1e6, 1), "ms_per_step": round(1000 * t / steps, 3)}
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy. Within DUMP_LIMIT_BYTES in all: an array over its
+    equal share of the limit is stored as a fixed seeded sample of its flattened elements (sorted indices)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def host_decode_rates(seconds=1.0):
     """Host JPEG entropy decode per core (the Huffman half of the drop-in's GPU decode, sp_jpeg_decode_coefs, one
     thread) and Pillow's whole decode (what the reference runs, serve.py:96-97), images/s per core, for the
@@ -626,7 +671,7 @@ def main():
     sync()
 
     rec, rec_timed = None, None
-    if set_hook is not None and not args.no_events:
+    if set_hook is not None and args.full and not args.no_events:
         import torch
 
         dom = DOMINANT_MODE[args.precision]
@@ -646,6 +691,8 @@ def main():
     barrier()
     if set_hook is not None:
         set_hook(None)
+    if args.dump_outputs and rank == 0 and getattr(step, "outputs", None) is not None:
+        dump_outputs(args.dump_outputs, step.outputs())  # before any further pass overwrites them
     mine = t1 - t0
     elapsed = max_over_ranks(mine)
     B = args.batch
@@ -728,7 +775,7 @@ def main():
             json.dump(rec.by_shape(), f, indent=1)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.stub_step_ms is None:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.stub_step_ms is None:
         try:
             cpu = cpu_baseline(step.cfg, step.weights, args.cpu_baseline_seconds, args.cpu_baseline_batch)
         except Exception as e:  # keep the GPU line even if the host path is unavailable
@@ -736,7 +783,7 @@ def main():
                    "sample": f"unavailable: {type(e).__name__}: {e}"}
 
     supply = None
-    if (rank == 0 and world == 1 and not args.no_input_supply and args.stub_step_ms is None
+    if (rank == 0 and world == 1 and args.full and not args.no_input_supply and args.stub_step_ms is None
             and getattr(step, "input_supply", None) is not None):
         try:
             v_host, h2d = step.input_supply(args.steps, args.warmup)
@@ -755,7 +802,7 @@ def main():
             supply = {"error": f"{type(e).__name__}: {e}"}
 
     lat = None
-    if rank == 0 and world == 1 and args.latency_iters > 0 and args.stub_step_ms is None:
+    if rank == 0 and world == 1 and args.full and args.latency_iters > 0 and args.stub_step_ms is None:
         try:
             from spotter_amd import SpotterForObjectDetection
             from spotter_amd.config import PRESETS

@@ -208,6 +208,29 @@ def test_bench_launcher_fails_fast_when_a_replica_dies(fail_rank):
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_dump_outputs_and_full_switch(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as <name>.npy, 64 MB at the most in all (an array over its share
+    becomes the same seeded sample on every call); --detail belongs to --full and a plain run refuses it."""
+    monkeypatch.syspath_prepend(ROOT)
+    import bench
+
+    small = np.arange(12, dtype=np.float32).reshape(3, 4)
+    big = np.arange(9 << 20, dtype=np.float32)  # 37.7 MB: over the 32 MB share of two arrays
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    got = np.load(tmp_path / "a" / "small.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    s = np.load(tmp_path / "a" / "big.npy")
+    assert s.nbytes == 32_000_000 and np.all(np.diff(s) > 0)  # a sample without repeats, in index order
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_LIMIT_BYTES
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--detail", str(tmp_path / "d.json")])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--detail", str(tmp_path / "d.json")])
+    assert bench.parse().full
+
+
 @pytest.mark.parametrize("preset", ["r18vd", "r101vd"])
 def test_config_from_hf_reads_hf_config_json(preset, tmp_path):
     """config.json as HF itself writes it (RTDetrV2Config.save_pretrained) → the same SpotterConfig as the

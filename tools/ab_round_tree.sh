@@ -4,7 +4,7 @@
 # .gpurunignore drops ./_abtree by default: narrow it to ./_abtree/spotter_amd/_build for the run.
 set -euo pipefail
 OUT=${1:-gpurun_out/abtree}; mkdir -p $OUT
-B="python3 -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --latency-iters 0 --no-events"
+B="python3 -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --latency-iters 0 --no-events"
 for r in 1 2; do
   for T in head base; do
     D=.; X=--no-input-supply  # (the round-start bench has no input-supply leg and no flag for it)

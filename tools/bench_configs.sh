@@ -6,7 +6,7 @@
 set -euo pipefail
 OUT=gpurun_out/${1:-cfg}
 mkdir -p "$OUT"
-B="python3 -u bench.py --no-cpu-baseline --latency-iters 0"
+B="python3 -u bench.py --full --no-cpu-baseline --latency-iters 0"
 timeout -k 10 300 $B --preset r18vd --precision bf16 --batch 256 > "$OUT/c3_r18vd_bf16_bs256.log" 2>&1
 tail -1 "$OUT/c3_r18vd_bf16_bs256.log" | cut -c1-200
 timeout -k 10 300 $B --size 1280 --batch 8 > "$OUT/c5_r101vd_1280_bs8.log" 2>&1

@@ -17,7 +17,7 @@ import torch
 from spotter_amd import ops
 from spotter_amd.ops import view
 
-# (n, h, w, cin, cout, k, stride, act, residual, launches per bs32 step)  — from bench.py --detail
+# (n, h, w, cin, cout, k, stride, act, residual, launches per bs32 step)  — from bench.py --full --detail
 SHAPES = [
     (32, 80, 80, 384, 384, 3, 1, None, False, 3),       # 0  CCFM 3x3 @80²         13.3 ms/step fp32
     (32, 40, 40, 256, 256, 3, 1, "relu", False, 22),    # 1  stage3 3x3            12.4

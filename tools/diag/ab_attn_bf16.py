@@ -8,7 +8,7 @@ import spotter_amd.engine as eng  # noqa: E402
 
 eng.ATTN_BF16 = sys.argv[1] == "on"
 args = ["--preset", "r18vd", "--precision", "bf16", "--batch", "256"] if sys.argv[2] == "c3" else ["--precision", "bf16"]
-sys.argv = ["bench.py", "--no-cpu-baseline", "--latency-iters", "0"] + args
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--latency-iters", "0"] + args
 import bench  # noqa: E402
 
 sys.exit(bench.main())

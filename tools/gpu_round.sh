@@ -13,10 +13,10 @@ export TMPDIR=/tmp
 timeout -k 10 600 python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread \
   > "$OUT/gpu_tests.log" 2>&1
 tail -3 "$OUT/gpu_tests.log"
-timeout -k 10 420 python3 -u bench.py > "$OUT/bench.log" 2>&1
+timeout -k 10 420 python3 -u bench.py --full > "$OUT/bench.log" 2>&1
 tail -1 "$OUT/bench.log"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench \
-  -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --latency-iters 0 > "$OUT/prof.log" 2>&1
+  -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --latency-iters 0 > "$OUT/prof.log" 2>&1
 python3 tools/stats_classes.py "$(find "$OUT/prof" -name '*kernel_stats.csv' | head -1)" \
   --csv-out "$OUT/kernel_stats.csv" > "$OUT/kernel_classes.json"
 bash tools/pmc_bench.sh "$OUT/pmc"

@@ -28,7 +28,7 @@ def main():
     ap.add_argument("--min-gain", type=float, default=0.02)
     ap.add_argument("--table", default=TABLE, help="the tile_table.h to update (default: the library's)")
     ap.add_argument("--detail", action="append", default=[],
-                    help="bench.py --detail file: its Winograd component GEMMs (batched, tiled by wino_gemm's own "
+                    help="bench.py --full --detail file: its Winograd component GEMMs (batched, tiled by wino_gemm's own "
                          "rule, not the table) are skipped")
     a = ap.parse_args()
     import ast

@@ -13,13 +13,13 @@ if [ "$PART" = a ]; then
   timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
   tail -1 $OUT/smoke.log
   bash tools/pmc_bench.sh $OUT/pmc_c2 > $OUT/pmc_c2.log 2>&1
-  timeout -k 10 600 python3 -u bench.py > $OUT/bench.log 2>&1
+  timeout -k 10 600 python3 -u bench.py --full > $OUT/bench.log 2>&1
   tail -1 $OUT/bench.log | cut -c1-200
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --latency-iters 0 > $OUT/prof.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --latency-iters 0 > $OUT/prof.log 2>&1
   python3 tools/stats_classes.py "$(find $OUT/prof -name '*kernel_stats.csv' | head -1)" --csv-out $OUT/kernel_stats.csv > $OUT/kernel_classes.json
   echo r5_final a done
 else
-  B="python3 -u bench.py --no-cpu-baseline --latency-iters 0"
+  B="python3 -u bench.py --full --no-cpu-baseline --latency-iters 0"
   for cfg in "c3:--preset r18vd --precision bf16 --batch 256" "c2bf16:--precision bf16" "c5:--size 1280 --batch 8" \
              "c5mixed:--size 1280 --batch 8 --stream mixed"; do
     name=${cfg%%:*}; args=${cfg#*:}

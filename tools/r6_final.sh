@@ -15,9 +15,9 @@ if [ "$PART" = a ]; then
   tail -1 $OUT/smoke.log
   bash tools/pmc_bench.sh $OUT/pmc_c2 > $OUT/pmc_c2.log 2>&1
   cp profiles/pmc_traffic.json $OUT/pmc_traffic_a.json
-  timeout -k 10 600 python3 -u bench.py --steps 20 --warmup 5 > $OUT/bench.log 2>&1
+  timeout -k 10 600 python3 -u bench.py --full --steps 20 --warmup 5 > $OUT/bench.log 2>&1
   tail -1 $OUT/bench.log | cut -c1-200
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --latency-iters 0 --no-input-supply > $OUT/prof.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --latency-iters 0 --no-input-supply > $OUT/prof.log 2>&1
   python3 tools/stats_classes.py "$(find $OUT/prof -name '*kernel_stats.csv' | head -1)" --csv-out $OUT/kernel_stats.csv > $OUT/kernel_classes.json
   set +e
   SPOTTER_HIP_LIB=spotter_amd/_bounds/libspotter_bounds.so timeout -k 10 900 python3 -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread > $OUT/gpu_tests_bounds.log 2>&1
@@ -28,7 +28,7 @@ if [ "$PART" = a ]; then
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "bounds suite rc=$rc"; exit $rc; fi
   echo r6_final a done
 else
-  B="python3 -u bench.py --no-cpu-baseline --latency-iters 0 --no-input-supply"
+  B="python3 -u bench.py --full --no-cpu-baseline --latency-iters 0 --no-input-supply"
   for cfg in "c3:--preset r18vd --precision bf16 --batch 256" "c2bf16:--precision bf16" "c5:--size 1280 --batch 8" \
              "c5mixed:--size 1280 --batch 8 --stream mixed"; do
     name=${cfg%%:*}; args=${cfg#*:}

@@ -2,7 +2,7 @@
 
     python tools/tune_conv.py <bench --detail JSON> [--out tune.json] [--reps 10] [--min-ms 0.05]
 
-Reads the per-shape timings `bench.py --detail` writes (shape key (M, Cout, K, k, stride, mode)),
+Reads the per-shape timings `bench.py --full --detail` writes (shape key (M, Cout, K, k, stride, mode)),
 rebuilds each GEMM (1×1 / linear: one row of M pixels; 3×3: 32 square images), times every tile
 configuration its operand mode has (sp_set_conv_config) and records the fastest. The winners become
 spotter_amd/csrc/tile_table.h (tools/gen_tile_table.py), the exact-shape part of the tile choice.

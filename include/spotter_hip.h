@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SP_ABI_VERSION 15
+#define SP_ABI_VERSION 16
 
 enum sp_act { SP_ACT_NONE = 0, SP_ACT_RELU = 1, SP_ACT_SILU = 2, SP_ACT_GELU = 3 };
 /* GEMM operand precision:
@@ -372,6 +372,57 @@ int sp_jpeg_enc_rgb(const uint8_t* rgb, int64_t row_stride, int32_t pixel_bytes,
 int64_t sp_jpeg_enc_max_bytes(const sp_jpeg_enc_layout* lay, int64_t nbits, int64_t comment_len);
 int sp_jpeg_enc_finish(const sp_jpeg_enc_layout* lay, const uint8_t* bits, int64_t nbits, const uint8_t* comment,
                        int64_t comment_len, uint8_t* out, int64_t out_cap, int64_t* out_len);
+
+/*
+ * Label drawing (ABI v16): serve.py:119-137 `ImageDraw.Draw(image)`, `draw.rectangle`, `draw.text`, whose Python
+ * half (colours, layout, anchors, stroke-then-fill) stays Pillow's and whose pixel half — ImagingDrawRectangle and
+ * ImagingFill2 with an "L" mask — runs here on the device image (spotter_amd/draw.py records, this applies).
+ * An operation covers the pixel rectangle [x0, x1] x [y0, y1] (inclusive, inside the image):
+ *   SP_DRAW_FILL   every pixel = ink;
+ *   SP_DRAW_BLEND  per channel out = DIV255(out * (255 - m) + ink_c * m), DIV255(a) = (t = a + 128,
+ *                  ((t >> 8) + t) >> 8) (Pillow's BLEND8: one rounding of the sum),
+ *                  m = masks[mask_off + (sy + y - y0)*mask_stride + sx + x - x0].
+ * Operations composite in list order at every pixel (the blend does not commute).
+ */
+enum sp_draw_kind { SP_DRAW_FILL = 0, SP_DRAW_BLEND = 1 };
+#define SP_DRAW_TILE_W 64 /* the pixel tile one workgroup owns */
+#define SP_DRAW_TILE_H 8
+typedef struct {
+  int32_t kind;             /* sp_draw_kind */
+  int32_t x0, y0, x1, y1;   /* inclusive pixel rectangle, 0 <= x0 <= x1 < width, 0 <= y0 <= y1 < height */
+  uint32_t ink;             /* r | g << 8 | b << 16 (Pillow's draw_ink for RGB) */
+  int64_t mask_off;         /* blend: byte offset of the mask's first row in the mask bytes */
+  int32_t mask_stride;      /* blend: bytes between mask rows */
+  int32_t sx, sy;           /* blend: the mask sample that falls on pixel (x0, y0) */
+  int32_t reserved;
+} sp_draw_op;
+/* One touched tile: pixels [tx*64, +64) x [ty*8, +8) and its operations refs[first : first + count), ascending. */
+typedef struct {
+  int32_t tx, ty;
+  int32_t first, count;
+} sp_draw_tile;
+/* The packed table sp_draw_pack writes and sp_draw_rgb reads: this header at byte 0, then the sections at the
+ * given byte offsets (each 16-byte aligned): ops (sp_draw_op[n_ops]), tiles (sp_draw_tile[n_tiles], ascending by
+ * (ty, tx), their ref ranges back to back), refs (int32[n_refs] operation indices), masks (mask_bytes bytes). */
+typedef struct {
+  int32_t n_ops, n_tiles, n_refs;
+  int32_t height, width;    /* the image the tiles were binned for */
+  int32_t reserved;
+  int64_t ops_off, tiles_off, refs_off, masks_off, mask_bytes;
+  int64_t total_bytes;
+} sp_draw_table;
+/* Host: bin the operations into the tiles they touch and write the packed table (header, operations, tile
+ * bins, mask bytes) into out. *need is the table's size; when out is NULL or out_cap < *need nothing else is
+ * written (call again with a larger buffer). No device call: safe without a GPU. */
+int sp_draw_pack(const sp_draw_op* ops, int32_t n_ops, const uint8_t* masks, int64_t mask_bytes, int32_t height,
+                 int32_t width, void* out, int64_t out_cap, int64_t* need);
+/* Device: apply a packed table to rgb (uint8 [height, width, 3] rows row_stride bytes apart) in place, in ONE
+ * launch with one workgroup per touched tile; every thread keeps four adjacent pixels in registers and walks its
+ * tile's operations in list order. table_host is the table as packed (read here, before the launch, to refuse
+ * an operation outside the image, a mask range outside the mask bytes, unordered or overlapping tile ranges: <0,
+ * nothing launched); table_dev is its device copy (the caller's one H2D copy, ordered before this call on stream). */
+int sp_draw_rgb(uint8_t* rgb, int32_t height, int32_t width, int64_t row_stride, const void* table_host,
+                const void* table_dev, int64_t table_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ import threading
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPOTTER_HIP_LIB", os.path.join(HERE, "libspotter_hip.so"))
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -81,6 +81,27 @@ class SpJpegEncLayout(C.Structure):
     ]
 
 
+class SpDrawOp(C.Structure):
+    _fields_ = [
+        ("kind", i32), ("x0", i32), ("y0", i32), ("x1", i32), ("y1", i32), ("ink", C.c_uint32),
+        ("mask_off", i64), ("mask_stride", i32), ("sx", i32), ("sy", i32), ("reserved", i32),
+    ]
+
+
+class SpDrawTile(C.Structure):
+    _fields_ = [("tx", i32), ("ty", i32), ("first", i32), ("count", i32)]
+
+
+class SpDrawTable(C.Structure):
+    _fields_ = [
+        ("n_ops", i32), ("n_tiles", i32), ("n_refs", i32), ("height", i32), ("width", i32), ("reserved", i32),
+        ("ops_off", i64), ("tiles_off", i64), ("refs_off", i64), ("masks_off", i64), ("mask_bytes", i64),
+        ("total_bytes", i64),
+    ]
+
+
+SP_DRAW_FILL, SP_DRAW_BLEND = 0, 1  # sp_draw_kind
+SP_DRAW_TILE_W, SP_DRAW_TILE_H = 64, 8
 SP_JPEG_UNSUPPORTED = -10
 SP_BUILD_FUSED_LN = 1  # sp_build_flags bits (include/spotter_hip.h)
 SP_BUILD_BOUNDS = 2
@@ -134,6 +155,8 @@ _SIGS = {
     "sp_jpeg_enc_rgb": (i32, [vp, i64, i32, C.POINTER(SpJpegEncLayout), vp, i64, vp, i64, vp, vp]),
     "sp_jpeg_enc_max_bytes": (i64, [C.POINTER(SpJpegEncLayout), i64, i64]),
     "sp_jpeg_enc_finish": (i32, [C.POINTER(SpJpegEncLayout), vp, i64, vp, i64, vp, i64, C.POINTER(i64)]),
+    "sp_draw_pack": (i32, [vp, i32, vp, i64, i32, i32, vp, i64, C.POINTER(i64)]),
+    "sp_draw_rgb": (i32, [vp, i32, i32, i64, vp, vp, i64, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

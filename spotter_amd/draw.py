@@ -1,5 +1,7 @@
-"""The label drawing of serve.py:119-137 (`ImageDraw.Draw(image)`, `draw.rectangle`, `draw.text`), kept on the
-host in Pillow's own code, with one change: the default font's glyph masks are memoised.
+"""The label drawing of serve.py:119-137 (`ImageDraw.Draw(image)`, `draw.rectangle`, `draw.text`): Pillow's own
+Python code, with two changes. The default font's glyph masks are memoised (below), and on a GPU-decoded image
+that has no host pixels the C core object behind `ImageDraw.draw` is a recorder whose fills and blends run on the
+GPU (second half of this file: DeviceDraw, DrawList).
 
 Measured on the MI355X box's EPYC host (tools/detect_path.py, profiles/r5/jpeg/): drawing the 16 labels of a
 /detect response takes 6.3 ms, nearly all of it FreeType rendering the same few strings (the amenity names of
@@ -21,12 +23,16 @@ byte-identical on the GPU box).
 """
 from __future__ import annotations
 
+import ctypes as C
+import struct
 import threading
 import types
 from collections import OrderedDict
 
+from PIL import Image as _PILImage
 from PIL import ImageDraw as _PILDraw
 from PIL import ImageFont as _PILFont
+from PIL import ImagePath as _PILPath
 
 # the hinted origin moves to the next pixel from these fractions on (26.6 fixed point; y points down in the
 # image and up in FreeType, hence the different half-way point)
@@ -56,12 +62,37 @@ class _MemoFont(_PILFont.FreeTypeFont):
         self._no_memo: set = set()
         self._exact: OrderedDict = OrderedDict()  # (string, options, exact start) -> (mask, offset)
         self.memo_stats = {"hits": 0, "exact_hits": 0, "renders": 0, "bypass": 0}
+        # id(mask) -> its bytes (None until DeviceDraw first asks) for exactly the masks _exact and _memo hold:
+        # entries leave with their mask, so an id in here always names a live mask of this font
+        self._held: dict = {}
+        self._memo_ids: set = set()
+
+    def _release(self, val):
+        if val is not None and id(val[0]) not in self._memo_ids:
+            self._held.pop(id(val[0]), None)
 
     def _exact_put(self, ekey, val):
         with self._memo_lock:
+            old = self._exact.get(ekey)
             self._exact[ekey] = val
+            if old is not None and old[0] is not val[0]:
+                self._release(old)
+            self._held.setdefault(id(val[0]), None)
             if len(self._exact) > self.EXACT_CAP:
-                self._exact.popitem(last=False)
+                self._release(self._exact.popitem(last=False)[1])
+
+    def mask_bytes(self, mask):
+        """The bytes of a mask this font holds in its caches (shared objects nothing writes to), kept with it for
+        the device draw's blends; None for any other object."""
+        b = self._held.get(id(mask), self)
+        if b is self:
+            return None
+        if b is None:
+            b = _tobytes(mask)
+            with self._memo_lock:
+                if id(mask) in self._held:
+                    self._held[id(mask)] = b
+        return b
 
     def getmask2(self, text, mode="", *args, start=None, **kwargs):
         if mode not in ("", "L", "1"):
@@ -111,10 +142,18 @@ class _MemoFont(_PILFont.FreeTypeFont):
             elif first[0] != tuple(start):  # a second fraction of the class: verify before memoising
                 if first[1] == sig:
                     self._memo[key] = (mask, offset)
+                    self._memo_ids.add(id(mask))
+                    self._held.setdefault(id(mask), None)
                 else:
                     self._no_memo.add(key)
                 del self._pending[key]
         return mask, offset
+
+
+def _tobytes(mask) -> bytes:
+    im = _PILImage.Image()
+    im._im, im._mode, im._size = mask, mask.mode, mask.size
+    return im.tobytes()
 
 
 _font = None
@@ -134,9 +173,228 @@ def memo_default_font() -> _MemoFont:
         return _font
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# Drawing on a device image. Pillow's ImageDraw does its colour parsing, text layout, anchors
+# and stroke-then-fill order in Python and reaches the pixels, for everything serve.py draws, through two methods
+# of its C core object `self.draw`: draw_rectangle and draw_bitmap (plus draw_ink). DeviceDraw is that same
+# Python class with `self.draw` replaced by a recorder, which turns the two calls into the fill / blend operations
+# of sp_draw_rgb (include/spotter_hip.h) on the image's draw list; the image applies the list on the GPU before
+# anything reads its pixels (spotter_amd/jpeg.py DeviceRGBImage.flush). Anything else hands over to Pillow.
+
+_OP = struct.Struct("<5iIq4i")  # sp_draw_op (tests/test_draw_device.py checks the layout against the header)
+_pack = _OP.pack
+_FILL, _BLEND = 0, 1
+_COORD_MAX = 1 << 30  # coordinates beyond this (or NaN / inf) are left to Pillow's own int casts
+
+
+class DrawList:
+    """The recorded operations of one image, in call order: packed sp_draw_op records and the bytes of the "L"
+    masks they blend. Rectangles are clipped to the image here; an operation that misses it is dropped."""
+
+    def __init__(self, width: int, height: int):
+        self.width, self.height = int(width), int(height)
+        self.clear()
+
+    def clear(self):
+        self.ops: list = []
+        self.masks: list = []
+        self.mask_bytes = 0
+        self._mask_at: dict = {}  # id(mask bytes) -> offset: a mask drawn twice is stored once
+
+    def __len__(self):
+        return len(self.ops)
+
+    def fill(self, x0, y0, x1, y1, ink):
+        """Every pixel of [x0, x1] x [y0, y1] (inclusive), clipped to the image, becomes the ink."""
+        if x0 < 0:
+            x0 = 0
+        if y0 < 0:
+            y0 = 0
+        if x1 >= self.width:
+            x1 = self.width - 1
+        if y1 >= self.height:
+            y1 = self.height - 1
+        if x0 <= x1 and y0 <= y1:
+            self.ops.append(_pack(_FILL, x0, y0, x1, y1, ink & 0xFFFFFF, 0, 0, 0, 0, 0))
+
+    def blend(self, x, y, mask: bytes, mw, mh, ink):
+        """An "L" mask of mw x mh bytes placed at (x, y), clipped to the image (Paste.c ImagingFill2)."""
+        x0, y0, x1, y1 = (x if x > 0 else 0), (y if y > 0 else 0), x + mw - 1, y + mh - 1
+        if x1 >= self.width:
+            x1 = self.width - 1
+        if y1 >= self.height:
+            y1 = self.height - 1
+        if x0 > x1 or y0 > y1:
+            return
+        off = self._mask_at.get(id(mask))
+        if off is None:
+            off = self._mask_at[id(mask)] = self.mask_bytes
+            self.masks.append(mask)  # kept alive here, so its id stays its own until clear()
+            self.mask_bytes += len(mask)
+        self.ops.append(_pack(_BLEND, x0, y0, x1, y1, ink & 0xFFFFFF, off, mw, x0 - x, y0 - y, 0))
+
+    def pack(self, out=None, cap=0) -> int:
+        """sp_draw_pack: bin the operations into tiles and write the packed table (header, operations, tile bins,
+        mask bytes) to the host address `out` when it fits in `cap` bytes. Returns the bytes the table needs."""
+        from ._lib import lib
+
+        need = C.c_int64()
+        L = lib()
+        if L.sp_draw_pack(b"".join(self.ops), len(self.ops), b"".join(self.masks), self.mask_bytes, self.height,
+                          self.width, out, cap, C.byref(need)):
+            raise RuntimeError(f"sp_draw_pack: {L.sp_last_error().decode(errors='replace')}")
+        return need.value
+
+    def packed(self) -> bytes:
+        """The packed table as bytes (tests; the image packs straight into its pinned staging buffer)."""
+        n = self.pack()
+        buf = C.create_string_buffer(n)
+        self.pack(C.addressof(buf), n)
+        return buf.raw
+
+
+# Pillow's core draw object on a 1x1 RGB image: draw_ink and the argument checks of draw_rectangle are its own
+# (same values, same exceptions and messages); whatever it draws lands in the scratch pixel.
+_SCRATCH = _PILImage.core.draw(_PILImage.core.fill("RGB", (1, 1)), 0)
+
+
+def _bytes_of(mask) -> bytes:
+    """The bytes of an "L" core image: kept with the mask when it is one the memoising default font holds (the
+    same object comes back for a repeated label), read afresh for any other font's render or a caller's bitmap."""
+    f = _font
+    b = f.mask_bytes(mask) if f is not None else None
+    return _tobytes(mask) if b is None else b
+
+
+def _ints(xy, n):
+    """The n doubles Pillow's PyPath_Flatten reads from xy, cast to int as its C code does (toward zero); None
+    where the cast is not defined in Python (NaN, inf) or the value is beyond any image."""
+    plain = type(xy) in (list, tuple) and len(xy) == n
+    if plain:
+        for v in xy:
+            if type(v) is not float and type(v) is not int:
+                plain = False
+                break
+    if not plain:
+        xy = _PILPath.Path(xy).tolist(True)
+        if len(xy) != n:
+            return None
+    try:
+        out = [int(v) for v in xy]
+    except (ValueError, OverflowError):
+        return None
+    if min(out) <= -_COORD_MAX or max(out) >= _COORD_MAX:
+        return None
+    return out
+
+
+class _Recorder:
+    """Stands where ImageDraw keeps its C core draw object. draw_rectangle and draw_bitmap append to the image's
+    draw list by Pillow's rules (Draw.c ImagingDrawRectangle, Paste.c ImagingFill2); every other method hands the
+    image over to Pillow."""
+
+    def __init__(self, owner):
+        self._owner = owner
+        self._image = owner._image
+        self.draw_ink = _SCRATCH.draw_ink
+
+    def draw_rectangle(self, xy, ink, fill, width=0):
+        _SCRATCH.draw_rectangle(xy, ink, fill, width)  # Pillow's own argument errors, at the call
+        c = _ints(xy, 4)
+        # (an image that has host pixels by now — somebody loaded it meanwhile — is Pillow's to draw on)
+        if c is None or self._image._im is not None:
+            return self._owner._hand_over().draw_rectangle(xy, ink, fill, width)
+        lst = self._image._draw_list
+        x0, y0, x1, y1 = c
+        if fill:
+            lst.fill(x0, y0, x1, y1, ink)
+            return
+        w = width or 1
+        if w < 0:
+            return
+        # ImagingDrawRectangle, outline: for i < w the rows y0 + i and y1 - i over x0..x1, then the columns x1 - i
+        # and x0 + i from row y0 + w towards row y1 - w + 1, half-open in the direction of travel (Draw.c line32
+        # draws |dy| points from the start). One ink, so the order among the four pieces does not matter.
+        lst.fill(x0, y0, x1, y0 + w - 1, ink)
+        lst.fill(x0, y1 - w + 1, x1, y1, ink)
+        ys, ye = y0 + w, y1 - w + 1
+        if ye != ys:
+            ra, rb = (ys, ye - 1) if ye > ys else (ye + 1, ys)
+            lst.fill(x1 - w + 1, ra, x1, rb, ink)
+            lst.fill(x0, ra, x0 + w - 1, rb, ink)
+
+    def draw_bitmap(self, xy, mask, ink):
+        if type(xy) is tuple and len(xy) == 2 and type(xy[0]) is int and type(xy[1]) is int:
+            c = xy if -_COORD_MAX < xy[0] < _COORD_MAX and -_COORD_MAX < xy[1] < _COORD_MAX else None
+        else:
+            c = _ints(xy, 2)
+        if (c is None or self._image._im is not None or getattr(mask, "mode", None) != "L"
+                or type(ink) is not int):
+            return self._owner._hand_over().draw_bitmap(xy, mask, ink)
+        mw, mh = mask.size
+        self._image._draw_list.blend(c[0], c[1], _bytes_of(mask), mw, mh, ink)
+
+    def __getattr__(self, name):  # draw_lines, draw_polygon, draw_ellipse, ...: Pillow's, on the host image
+        if name.startswith("__"):
+            raise AttributeError(name)
+        return getattr(self._owner._hand_over(), name)
+
+
+class DeviceDraw(_PILDraw.ImageDraw):
+    """Pillow's ImageDraw on a device image that has no host pixels: the same attributes and all of Pillow's
+    Python-level logic, with the C core draw object replaced by a recorder. The image is not loaded."""
+
+    def __init__(self, im):
+        # ImageDraw.__init__ for mode "RGB" without im._ensure_mutable() / im.im
+        self.palette = None
+        self._image = im
+        self.mode = "RGB"
+        self.draw = _Recorder(self)
+        self.ink = self.draw.draw_ink(-1)
+        self.fontmode = "L"
+        self.fill = False
+        if self.font is None:
+            self.font = memo_default_font()
+
+    @property
+    def im(self):
+        """Pillow's text(embedded_color=True) pastes into draw.im: reading it hands the image over to Pillow."""
+        self._hand_over()
+        return self._image.im
+
+    @im.setter
+    def im(self, value):
+        raise AttributeError("DeviceDraw.im is the image's own core object")
+
+    def _hand_over(self):
+        """Flush what was recorded, materialise the host image as before this class existed, and draw on it with
+        Pillow's real core object from here on."""
+        if isinstance(self.draw, _Recorder):
+            self._image.load()
+            self.draw = _PILImage.core.draw(self._image.im, 0)
+        return self.draw
+
+
+_lib_ok = None
+
+
+def _library_loadable() -> bool:
+    global _lib_ok
+    if _lib_ok is None:
+        try:
+            from ._lib import lib
+
+            lib()
+            _lib_ok = True
+        except (RuntimeError, OSError):
+            _lib_ok = False
+    return _lib_ok
+
+
 class _DrawModule(types.ModuleType):
     """`PIL.ImageDraw` as serve.py sees it after the drop-in (module scope): every attribute is
-    Pillow's; `Draw(im)` is Pillow's ImageDraw on `im` whose default font memoises its glyph masks."""
+    Pillow's; `Draw(im)` is Pillow's ImageDraw on `im` whose default font memoises its glyph masks. For a device
+    image that has not been loaded to the host it is a DeviceDraw: the same class, recording for the GPU."""
 
     def __init__(self):
         super().__init__("PIL.ImageDraw", _PILDraw.__doc__)
@@ -145,6 +403,9 @@ class _DrawModule(types.ModuleType):
         return getattr(_PILDraw, name)
 
     def Draw(self, im, mode=None):  # noqa: N802 - Pillow's name
+        if (mode in (None, "RGB") and getattr(im, "_draw_list", None) is not None and im._im is None
+                and im.mode == "RGB" and not im.readonly and _library_loadable()):
+            return DeviceDraw(im)
         d = _PILDraw.Draw(im, mode)
         if d.font is None:
             d.font = memo_default_font()

@@ -318,45 +318,66 @@ def decoder(device=None) -> JpegDecoder:
 from PIL import Image as _PILImage  # noqa: E402  (Pillow is a dependency of the reference app)
 from PIL import JpegImagePlugin as _JpegPlugin  # noqa: E402
 
+from .draw import DrawList  # noqa: E402
+
 
 class DeviceRGBImage(_PILImage.Image):
-    """A PIL RGB image decoded on the GPU. `spotter_device_rgb` holds the uint8 [H, W, 3] device tensor that
-    SpotterImageProcessor reads in place; the host pixels (what the unchanged draw / JPEG-encode tail of
-    serve.py:119-142 needs) arrive by an async D2H copy on a side stream and are materialised only when
-    Pillow first needs them (load()). convert("RGB") / copy() of a not-yet-loaded image stay lazy. `info` is
-    the source file's, as Pillow's JpegImageFile would carry it (its "comment" is written back by save)."""
+    """A PIL RGB image whose pixels live on the GPU: the uint8 [H, W, 3] device tensor `spotter_device_rgb`, which
+    SpotterImageProcessor reads in place, the drop-in's ImageDraw draws on (spotter_amd/draw.py DeviceDraw records
+    into `_draw_list`; flush() applies the list with one sp_draw_rgb launch before anything reads the pixels) and
+    save(format="JPEG") encodes from. The host pixels are made only when Pillow itself needs them (load(): a
+    device → host copy on demand; from then on the image is an ordinary loaded PIL image, drawn on by Pillow and
+    uploaded by save). convert("RGB") / copy() of a not-yet-loaded image stay lazy and share the tensor until one
+    of them is drawn on. `info` is the source file's, as Pillow's JpegImageFile would carry it (its "comment" is
+    written back by save)."""
 
-    def __init__(self, rgb_dev: torch.Tensor, host=None, done=None, info=None):
+    def __init__(self, rgb_dev: torch.Tensor, info=None, shared=False):
         super().__init__()
         H, W, _ = rgb_dev.shape
         self._mode = "RGB"
         self._size = (int(W), int(H))
-        self.spotter_device_rgb = rgb_dev
+        self._dev = rgb_dev
+        self._owns = not shared  # a shared tensor is cloned before the first draw reaches it
+        self._draw_list = DrawList(W, H)
         if info:
             self.info = dict(info)
-        if host is None:
-            # the host copy as RGBX rows (X = 255): Pillow's own 4-byte pixel layout, which load() unpacks with a
-            # straight 4-byte copy (0.48 against 0.98 ms for packed RGB through a bytes object on the CPU here)
-            dev = rgb_dev.device
-            host = torch.empty((H, W, 4), dtype=torch.uint8, pin_memory=True)
-            side = _side_stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                x4 = torch.full((H, W, 4), 255, dtype=torch.uint8, device=dev)
-                x4[..., :3].copy_(rgb_dev)
-                host.copy_(x4, non_blocking=True)
-                done = torch.cuda.Event()
-                done.record(side)
-            rgb_dev.record_stream(side)
-            x4.record_stream(side)
-        self._pending = (host, done)
+
+    @property
+    def spotter_device_rgb(self) -> torch.Tensor:
+        """The device pixels with every recorded draw applied."""
+        self.flush()
+        return self._dev
+
+    def flush(self):
+        """Apply the recorded draw operations on the current stream: one packed table (operations, tile bins, mask
+        bytes) in the device's pinned staging buffer, one H2D copy, one sp_draw_rgb launch."""
+        lst = self._draw_list
+        if not len(lst):
+            return
+        t = self._dev
+        if not self._owns or t.stride(2) != 1 or t.stride(1) != 3 or t.stride(0) < 3 * t.shape[1]:
+            t = self._dev = t.clone(memory_format=torch.contiguous_format)  # device to device
+            self._owns = True
+        _draw_stage(t.device).run(lst, t)
+        lst.clear()
 
     def _lazy_copy(self):
-        return DeviceRGBImage(self.spotter_device_rgb, *self._pending, info=self.info)
+        t = self.spotter_device_rgb  # pending draws are applied first (by the owner in place, else to a clone)
+        self._owns = False  # from here on neither image owns the tensor
+        return DeviceRGBImage(t, info=self.info, shared=True)
 
     def load(self):
-        if self._im is None and getattr(self, "_pending", None) is not None:
-            host, done = self._pending
+        if self._im is None and getattr(self, "_dev", None) is not None:
+            # the host copy as RGBX rows (X = 255): Pillow's own 4-byte pixel layout, which frombytes unpacks with
+            # a straight 4-byte copy (0.48 against 0.98 ms for packed RGB through a bytes object)
+            t = self.spotter_device_rgb
+            H, W, _ = t.shape
+            x4 = torch.full((H, W, 4), 255, dtype=torch.uint8, device=t.device)
+            x4[..., :3].copy_(t)
+            host = torch.empty((H, W, 4), dtype=torch.uint8, pin_memory=True)
+            host.copy_(x4, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(t.device))
             done.synchronize()
             self.im = _PILImage.frombytes("RGB", self._size, memoryview(host.numpy()).cast("B"), "raw", "RGBX").im
         return super().load()
@@ -373,13 +394,65 @@ class DeviceRGBImage(_PILImage.Image):
 
     def save(self, fp, format=None, **params):
         """serve.py:140 `image.save(buffer, format="JPEG")`: encoded on the GPU, the bytes Pillow writes. An image
-        whose pixels never reached the host encodes from its device copy; once loaded (drawn on), its host
-        pixels are uploaded. Other formats, file names and options go to Pillow's own save."""
+        whose pixels never reached the host (drawn on through the drop-in's ImageDraw or not at all) encodes from
+        its device tensor, recorded draws applied first; once loaded (drawn on by Pillow), its host pixels are
+        uploaded. Other formats, file names and options go to Pillow's own save."""
         opts = _gpu_jpeg_options(self, fp, format, params)
         if opts is None:
             return super().save(fp, format, **params)
         src = self.spotter_device_rgb if self._im is None else self
-        fp.write(encoder(self.spotter_device_rgb.device).encode(src, *opts))
+        fp.write(encoder(self._dev.device).encode(src, *opts))
+
+
+class _DrawStage:
+    """Per-device staging of DeviceRGBImage.flush: a pinned host buffer the draw table is packed into and its
+    device copy, grown as needed and reused like JpegEncoder's (one flush at a time; the lock serialises callers)."""
+
+    def __init__(self, device):
+        self.dev = torch.device(device)
+        self._lock = threading.Lock()
+        self._stage = self._table = None
+        self._copied = None  # event: the last H2D copy out of the pinned buffer is done
+        self._done = None    # event: the last launch is done with the device table
+
+    def run(self, lst, rgb: torch.Tensor):
+        with self._lock:
+            L = lib()
+            cur = torch.cuda.current_stream(self.dev)
+            if self._copied is not None:
+                self._copied.synchronize()  # the pinned buffer is free again
+            cap = 0 if self._stage is None else self._stage.numel()
+            need = lst.pack(self._stage.data_ptr() if cap else None, cap)
+            if need > cap:
+                if self._done is not None:
+                    self._done.synchronize()  # the old device table goes back to the caching allocator
+                self._stage = JpegEncoder._grow(None, need, torch.uint8, pinned=True)
+                self._table = JpegEncoder._grow(None, need, torch.uint8, self.dev)
+                need = lst.pack(self._stage.data_ptr(), self._stage.numel())
+            if self._done is not None:
+                cur.wait_event(self._done)  # another stream's previous launch may still read the device table
+            self._table[:need].copy_(self._stage[:need], non_blocking=True)
+            self._copied = torch.cuda.Event()
+            self._copied.record(cur)
+            H, W, _ = rgb.shape
+            rc = L.sp_draw_rgb(rgb.data_ptr(), H, W, rgb.stride(0), self._stage.data_ptr(), self._table.data_ptr(),
+                               need, cur.cuda_stream)
+            if rc:
+                raise RuntimeError(f"sp_draw_rgb: {L.sp_last_error().decode(errors='replace')}")
+            self._done = torch.cuda.Event()
+            self._done.record(cur)
+
+
+_stages: dict = {}
+
+
+def _draw_stage(device) -> _DrawStage:
+    dev = torch.device(device)
+    with _dec_lock:
+        s = _stages.get(dev)
+        if s is None:
+            s = _stages[dev] = _DrawStage(dev)
+        return s
 
 
 _SUBSAMPLING = {-1: -1, 0: 0, 1: 1, 2: 2, "4:4:4": 0, "4:2:2": 1, "4:2:0": 2, "4:1:1": 2}
@@ -406,16 +479,6 @@ def _gpu_jpeg_options(im, fp, format, params):
         return None
     # (dpi, EXIF, ICC and XMP come from the save() arguments only, never from im.info: any of them → Pillow)
     return q, _SUBSAMPLING[sub], comment
-
-
-_sides: dict = {}
-
-
-def _side_stream(dev):
-    s = _sides.get(dev)
-    if s is None:
-        s = _sides[dev] = torch.cuda.Stream(dev)
-    return s
 
 
 def _device_image(im, data, device=None):

@@ -124,6 +124,8 @@ typedef struct {
  *           then [H*L*P*2, +H*L*P) attention logits (h, l*P + p)
  *   ref     [B*Q, 4] reference boxes (cx, cy, w, h) in (0, 1)
  *   out     [B*Q, ld_out] with column h*Dh + c
+ * Requires B, Q > 0, H*Dh a multiple of 64 <= 1024, 1 <= L <= 4, ld_off_aw >= H*L*P*3, ld_out >= H*Dh,
+ * ld_value >= value_col + H*Dh.
  */
 typedef struct {
   const float* value; int64_t ld_value; int32_t value_col;
@@ -266,7 +268,8 @@ int sp_attention_bf16(const float* q, int64_t ldq, const float* k, int64_t ldk, 
 int sp_msda(const sp_msda_desc* d, void* stream);
 /* Per row: top-k of x[r, 0:n] (values reduced by max over groups of `reduce_c` consecutive
  * columns first when reduce_c > 1; sigmoid applied first when apply_sigmoid), sorted by
- * value descending, ties by lower index. vals may be NULL. Requires k <= 512. */
+ * value descending, ties by lower index (-0.0 ties with +0.0 and is returned as +0.0). vals may be NULL.
+ * Requires k <= 512. */
 int sp_topk_rows(const float* x, int64_t ldx, int rows, int n, int reduce_c, int apply_sigmoid,
                  int k, float* vals, int32_t* idx, void* stream);
 /* out[r] = max_c x[r*ldx + c], c < C: the per-anchor class max in front of query selection

@@ -171,6 +171,13 @@ def load(path: str = LIB_PATH):
         raise RuntimeError(
             f"libspotter_hip.so not found at {path}; build it with `python -m spotter_amd.build_ext` "
             "(there is no CPU fallback)")
+    # torch first: its wheel bundles a HIP runtime (soname libamdhip64.so.7, found through libtorch_hip's
+    # $ORIGIN rpath under the name libamdhip64.so). Loaded after torch, this library binds to that copy by
+    # soname; loaded before it, this library brings in the system ROCm's copy and torch then loads its own
+    # beside it: two HIP runtimes in one process, and the first hipMalloc / hipMemcpy here fails (build()
+    # followed by smoke() in one process did: "coefficient upload failed").
+    import torch  # noqa: F401
+
     L = C.CDLL(path)
     for name, (res, args) in _SIGS.items():
         fn = getattr(L, name)

@@ -13,7 +13,9 @@
 namespace sp {
 namespace {
 
-__global__ __launch_bounds__(256) void msda_kernel(const sp_msda_desc d) {
+// The fallback for every accepted descriptor the vectorised forms do not take: one thread per channel, so a
+// workgroup is C = heads·head_dim threads, up to the 1024 sp_msda admits.
+__global__ __launch_bounds__(1024) void msda_kernel(const sp_msda_desc d) {
   const int t = threadIdx.x;
   const int h = t / d.head_dim;
   const int c = t - h * d.head_dim;
@@ -303,7 +305,17 @@ extern "C" int sp_msda(const sp_msda_desc* d, void* stream) {
   SP_ARG_CHECK(d && (d->value || d->value_bf16) && d->off_aw && d->ref && d->out, "sp_msda: null args");
   SP_ARG_CHECK(d->heads * d->head_dim <= 1024 && (d->heads * d->head_dim) % 64 == 0,
                "sp_msda: heads*head_dim must be a multiple of 64 <= 1024");
+  SP_ARG_CHECK(d->heads > 0 && d->head_dim > 0, "sp_msda: heads=%d head_dim=%d", d->heads, d->head_dim);
   SP_ARG_CHECK(d->levels >= 1 && d->levels <= 4 && d->points >= 1, "sp_msda: levels/points");
+  SP_ARG_CHECK(d->B > 0 && d->Q > 0, "sp_msda: B=%d Q=%d must be positive", d->B, d->Q);
+  SP_ARG_CHECK(d->ld_off_aw >= (int64_t)d->heads * d->levels * d->points * 3,
+               "sp_msda: ld_off_aw=%lld < heads*levels*points*3 = %lld", (long long)d->ld_off_aw,
+               (long long)d->heads * d->levels * d->points * 3);
+  SP_ARG_CHECK(d->ld_out >= (int64_t)d->heads * d->head_dim, "sp_msda: ld_out=%lld < heads*head_dim = %d",
+               (long long)d->ld_out, d->heads * d->head_dim);
+  SP_ARG_CHECK(d->value_col >= 0 && d->ld_value >= (int64_t)d->value_col + d->heads * d->head_dim,
+               "sp_msda: ld_value=%lld < value_col + heads*head_dim = %lld", (long long)d->ld_value,
+               (long long)d->value_col + d->heads * d->head_dim);
   int total = 0;
   for (int l = 0; l < d->levels; ++l) {
     SP_ARG_CHECK(d->level_start[l] == total, "sp_msda: level_start mismatch at %d", l);

@@ -21,8 +21,11 @@ constexpr int kMaxN = 36864;  // 144 KiB of keys: covers S = 33,600 at 1280² (L
 constexpr int kMaxK = 512;
 constexpr int kHist = 4;  // histogram copies (LDS: keys 144 KiB + 4 KiB + candidates 4 KiB)
 
+// -0.0 takes +0.0's key: the two compare equal, so they tie and the lower index wins (as torch.topk and a
+// stable sort order them); a value read back from a key (key2f) is then +0.0 for either.
 __device__ __forceinline__ uint32_t f2key(float f) {
   uint32_t u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float key2f(uint32_t k) {

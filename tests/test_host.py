@@ -55,6 +55,22 @@ def test_library_exports_every_header_symbol():
     assert L.sp_abi_version() == _lib.ABI_VERSION
 
 
+def test_loading_the_library_before_torch_maps_one_hip_runtime():
+    """A fresh process that loads the library first and imports torch afterwards (what build() followed by
+    smoke() does) must end up with one libamdhip64 mapped: torch's wheel bundles its own copy, and with two HIP
+    runtimes in the process the library's first hipMalloc / hipMemcpy fails. _lib.load() imports torch first."""
+    from spotter_amd.build_ext import LIB, build
+
+    if not os.path.exists(LIB):
+        build(verbose=False)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("from spotter_amd import _lib\n_lib.load()\nimport torch\n"
+            "paths = {ln.split()[-1] for ln in open('/proc/self/maps') if 'libamdhip64' in ln}\n"
+            "print(len(paths), sorted(paths))\n")
+    out = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, check=True).stdout
+    assert out.split()[0] == "1", out
+
+
 def test_ctypes_descriptors_match_the_header_layout(tmp_path):
     """The ctypes mirrors of the C-ABI descriptor structs (spotter_amd/_lib.py) have the header's size and
     field offsets, checked against a C program compiled from include/spotter_hip.h."""

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SP_ABI_VERSION 16
+#define SP_ABI_VERSION 17
 
 enum sp_act { SP_ACT_NONE = 0, SP_ACT_RELU = 1, SP_ACT_SILU = 2, SP_ACT_GELU = 3 };
 /* GEMM operand precision:
@@ -237,6 +237,16 @@ int sp_conv3x3_c32(const float* x, const float* wt, const float* scale, const fl
 int sp_conv3x3_c64_bf16(const uint16_t* x, int64_t ldx, const uint16_t* w16, const float* scale, const float* shift,
                         uint16_t* y, int64_t ldy, const uint16_t* res, int64_t ldr, int n, int h, int w, int act,
                         void* stream);
+/* The thin 3x3 stride-1 pad-1 convs of the fp32 path on the 3-way bf16 split (ABI v17): fp32 rows in and out,
+ * weights as the hi / mid / lo bf16 planes [3][Cout][9*Cin] (k in (tap, channel) order, planes plane_stride
+ * elements apart: the SP_PREC_F32X3 operand form), BN (scale, shift) + act (0 none, 1 relu). Direct LDS-halo
+ * convolutions, bit-identical to sp_conv2d's SP_PREC_F32X3 path on the same operands.
+ * sp_conv3x3_c64_x3: Cin 64 -> Cout 64 (the stage-0 bottleneck 3x3), rows ldx / ldy floats apart (% 4, >= 64).
+ * sp_conv3x3_c32_x3: Cin 32 -> Cout 32 or 64 (stem convs 2 / 3), dense rows. */
+int sp_conv3x3_c64_x3(const float* x, int64_t ldx, const uint16_t* w_planes, int64_t plane_stride, const float* scale,
+                      const float* shift, float* y, int64_t ldy, int n, int h, int w, int act, void* stream);
+int sp_conv3x3_c32_x3(const float* x, const uint16_t* w_planes, int64_t plane_stride, const float* scale,
+                      const float* shift, float* y, int n, int h, int w, int cout, int act, void* stream);
 /* nn.MaxPool2d(3, 2, 1) on NHWC (RN:88). y rows are ldy floats apart (ldy >= c, ldy % 4 == 0), so the
  * result can land in a channel slice of a wider buffer (the fused bottleneck shortcut, ABI v6). */
 int sp_maxpool3x3s2(const float* x, float* y, int64_t ldy, int n, int h, int w, int c, void* stream);

@@ -13,7 +13,7 @@ import threading
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPOTTER_HIP_LIB", os.path.join(HERE, "libspotter_hip.so"))
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -135,6 +135,8 @@ _SIGS = {
     "sp_conv3x3_c32_bf16": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "sp_conv3x3_c32": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "sp_conv3x3_c64_bf16": (i32, [vp, i64, vp, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp]),
+    "sp_conv3x3_c64_x3": (i32, [vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
+    "sp_conv3x3_c32_x3": (i32, [vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "sp_upsample2x_nearest": (i32, [vp, i64, vp, i64, i32, i32, i32, i32, vp]),
     "sp_layernorm": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, f32, vp]),
     "sp_layernorm_bf16": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, f32, vp]),

@@ -74,7 +74,7 @@ def _wkw(wq):
 
 
 class ConvW:
-    __slots__ = ("w", "cin", "cout", "k", "scale", "shift", "w16", "host", "wino", "mode")
+    __slots__ = ("w", "cin", "cout", "k", "scale", "shift", "w16", "host", "wino", "mode", "x3p")
 
     def __init__(self, w, cin, cout, k, scale, shift, w16=None, host=None, mode="f32"):
         self.w, self.cin, self.cout, self.k, self.scale, self.shift = w, cin, cout, k, scale, shift
@@ -82,6 +82,7 @@ class ConvW:
         self.mode = mode  # operand mode of w16: "f32" (none: fp32 MFMA), "bf16" (one plane), "x3" (three)
         self.host = host  # the packed fp32 [Cout, K] weights on the host (pack-time fusions read them)
         self.wino = None  # Winograd F(2x2, 3x3) weight planes when this stride-1 3x3 runs that way
+        self.x3p = None  # hi / mid / lo planes of a layer whose GEMM mode is "f32" but whose direct kernel is x3
 
 
 class LinW:
@@ -148,7 +149,8 @@ class Engine:
                  fold_repvgg: bool = True, precision: str = "fp32", fuse_shortcut: bool = True,
                  fuse_ln: bool = False, winograd: str | bool = "auto", wino_m: int = 4,
                  bf16_store: bool | None = None, direct_c32: bool = True,
-                 direct_c64_bf16: bool = True, splitk_combine: bool = False):
+                 direct_c64_bf16: bool = True, splitk_combine: bool = False, direct_c64_x3: bool = True,
+                 direct_c32_x3: bool = False):
         from ._lib import SP_BUILD_FUSED_LN, lib
 
         check_precision(precision)
@@ -202,6 +204,14 @@ class Engine:
         # the fp32-MFMA implicit GEMM
         self.direct_c32 = direct_c32
         self.direct_c64_bf16 = direct_c64_bf16  # the stage-0 3x3 (Cin 64 -> 64) on bf16 rows (sp_conv3x3_c64_bf16)
+        # the same conv in mode "x3" on fp32 rows (sp_conv3x3_c64_x3): direct LDS-halo kernel, bit-identical to the x3
+        # implicit GEMM it replaces, 1.65x per launch at bs32
+        self.direct_c64_x3 = direct_c64_x3
+        # under precision "fp32" only: the Cin-32 stem 3x3s on the split planes (sp_conv3x3_c32_x3, 1.49-1.59x per
+        # launch) instead of the exact-product sp_conv3x3_c32. Off by default: both are fp32-accurate, but the split
+        # rounds the 288-term sums differently, so the stem maps, and through the query selection the outputs,
+        # are not those of the exact-product kernel
+        self.direct_c32_x3 = direct_c32_x3
         # split-K GEMMs (the small-batch path) combine their partial sums inside the GEMM launch (per-context
         # arrival counters, sp_conv_desc.splitk_counters) instead of a second reduce launch: bit-identical, 303
         # instead of 438 launches per bs1 forward, but 4.786 against 4.714 ms per graph replay (the write-through
@@ -270,10 +280,16 @@ class Engine:
         """Per-layer GEMM mode. Under precision "fp32" both operand modes are fp32-accurate, so layers
         where the plain fp32 MFMA measured faster than the 6-MFMA split (tools/conv_bench.py,
         profiles/r1/conv_detail_*.json) take it: thin outputs (Cout <= 64: stem, stage-1), thin
-        reductions (K <= 64) and the decoder's M = B·300 linears."""
+        reductions (K <= 64) and the decoder's M = B·300 linears. The Cin-32 stem 3×3s are picked "f32" here too
+        and from C32_MIN_PIXELS up run on the exact-product direct kernel (sp_conv3x3_c32); with
+        Engine(direct_c32_x3=True) backbone() runs them on the split planes instead (ConvW.x3p, sp_conv3x3_c32_x3:
+        1.49-1.59× per launch, other roundings, so off by default)."""
         if mode == "x3" and self.precision == "fp32" and (cout <= 64 or kdim <= 64 or small_m):
             if cout == 64 and kdim >= 576 and not small_m:
-                return mode  # 3×3 64→64 (stage 1): the split kernel's 256×64 tile, 1.09× (conv_bench_thin_x3)
+                # 3×3 64→64 (stage 1) stays in the split mode: from C64_MIN_PIXELS up _cv runs it as the direct
+                # split kernel sp_conv3x3_c64_x3 (1.65× the implicit GEMM, profiles/direct_x3/); below that the
+                # split GEMM's 256×64 tile, 1.09× the fp32 MFMA (conv_bench_thin_x3)
+                return mode
             if (cout, kdim, small_m) in _X3_FASTER:
                 return mode
             return "f32"
@@ -310,6 +326,10 @@ class Engine:
         bb = "model.backbone.model"
         self.stem = [self._conv(p, f"{bb}.embedder.embedder.{i}.convolution.weight",
                                 f"{bb}.embedder.embedder.{i}.normalization", True) for i in range(3)]
+        if self.precision == "fp32" and self._conv_mode == "x3" and self.direct_c32_x3:
+            for cw in self.stem[1:]:  # the split planes of stem convs 2 / 3 for sp_conv3x3_c32_x3
+                if cw.cin == 32 and cw.k == 3 and cw.cout in (32, 64) and cw.mode == "f32":
+                    cw.x3p = torch.from_numpy(ops.split_bf16x3_host(cw.host)).to(self.dev)
         self.blocks = []
         for (s, i, lt, cin, cout, st, sc) in backbone_plan(cfg):
             pre = f"{bb}.encoder.stages.{s}.layers.{i}"
@@ -491,6 +511,10 @@ class Engine:
                 # the bf16 variant's stage-0 3x3: direct LDS-halo kernel, bit-identical to the implicit GEMM and
                 # 1.53x it at bs32 / bs256 (814 TF at C3; profiles/r3/bf16/ab_conv3x3_c64_bf16.jsonl)
                 return ops.conv3x3_c64_bf16(x, cw.w16, cw.scale, cw.shift, out, n, h, w, act=act, res1=res1)
+            rows4 = lambda v: not v.is_bf16 and v.ld % 4 == 0 and v.off % 4 == 0  # noqa: E731 (16-byte aligned fp32 rows)
+            if self.direct_c64_x3 and cw.mode == "x3" and res1 is None and rows4(x) and rows4(out):
+                # the fp32 path's stage-0 3x3: the direct split kernel, bit-identical to the x3 implicit GEMM
+                return ops.conv3x3_c64_x3(x, cw.w16, cw.scale, cw.shift, out, n, h, w, act=act)
         if cw.wino is not None and stride == 1 and not kw and not x.is_bf16 and self._wino_pays(n * h * w, cw.cin):
             wm = self.wino_m
             tiles = n * ((h + wm - 1) // wm) * ((w + wm - 1) // wm)
@@ -538,8 +562,13 @@ class Engine:
         ops.add_rows(x, addend, hp, rows, lw.k)
         return self._lin_op(hp, rows, lw, out)
 
+    # the direct 3×3 kernels run one persistent workgroup per CU over 256-pixel (8 × 32) tiles, and the GEMMs win on
+    # maps of a few tiles per CU: sp_conv3x3_c64_bf16 / sp_conv3x3_c64_x3 from 4 tiles per CU up (measured at bs32
+    # of 160² and bs8 of 320², 12.5 tiles per CU: 1.65x, profiles/direct_x3/ab_direct_x3.json)
     C64_MIN_PIXELS = 1 << 18
-    C32_MIN_PIXELS = 1 << 19  # sp_conv3x3_c32 from about 4 tiles per CU up (bs8 at 320²: 1.08-1.17x)
+    # sp_conv3x3_c32 / sp_conv3x3_c32_x3 from about 4 (512-pixel) / 8 tiles per CU up (sp_conv3x3_c32 at bs8 of
+    # 320²: 1.08-1.17x the GEMM; the x3 kernel was measured at bs32 of 320² and bs8 of 640² only, so it keeps the gate)
+    C32_MIN_PIXELS = 1 << 19
 
     def _direct_stem(self) -> bool:
         """The stem's first conv (Cin 3, K = 27) runs on the direct NCHW kernel (sp_stem_conv3x3s2_nchw, fp32
@@ -575,6 +604,12 @@ class Engine:
                 # A row per tap and wasted half a 64-wide tile on Cout 32)
                 ops.conv3x3_c32_bf16(view(src, cw.cin), cw.w16, cw.scale, cw.shift, view(dst, cw.cout), B, h1, w1,
                                      cw.cout, act=self.act_bb)
+            elif (c32 and self.direct_c32_x3 and cw.x3p is not None and self.precision == "fp32"
+                  and B * h1 * w1 >= self.C32_MIN_PIXELS):
+                # precision "fp32": the direct kernel on the 3-way split (bf16 MFMA pipe) instead of exact fp32
+                # products; "fp32-mfma" keeps sp_conv3x3_c32 below
+                ops.conv3x3_c32_x3(view(src, cw.cin), cw.x3p, cw.scale, cw.shift, view(dst, cw.cout), B, h1, w1,
+                                   cw.cout, act=self.act_bb)
             elif (c32 and self.direct_c32 and cw.mode == "f32" and not self.bf16_store
                   and B * h1 * w1 >= self.C32_MIN_PIXELS):
                 # the fp32 modes: the same direct kernel on fp32 rows with fp32 MFMAs (exact products): 1.24-1.29x

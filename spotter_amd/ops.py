@@ -392,6 +392,48 @@ def conv3x3_c64_bf16(x: V, w16: torch.Tensor, scale: torch.Tensor, shift: torch.
             2 * m * 64 * 576, 2 * (m * 64 + 64 * 576 + m * 64 * (2 if rp else 1)), (m, 64, 576, 3, 1, "bf16-direct"))
 
 
+def _x3_planes(wt_planes: torch.Tensor, numel: int, what: str):
+    if (wt_planes.dim() != 2 or wt_planes.shape[0] != 3 or wt_planes.shape[1] != numel
+            or wt_planes.dtype != torch.int16 or not wt_planes.is_contiguous() or not wt_planes.is_cuda):
+        raise ValueError(f"{what}: weight planes must be a contiguous int16 CUDA tensor [3, {numel}]")
+    return wt_planes.data_ptr(), wt_planes.shape[1]
+
+
+def conv3x3_c64_x3(x: V, wt_planes: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, y: V, n: int, h: int,
+                   w: int, act=None):
+    """The stage-0 3×3 (Cin 64 → 64) of the fp32 path on fp32 rows (channel-slice views allowed) and the
+    hi / mid / lo weight planes (split_bf16x3): the direct LDS-halo kernel sp_conv3x3_c64_x3, bit-identical to
+    conv2d(..., wt_planes=...)."""
+    if x.is_bf16 or y.is_bf16 or x.ld % 4 or x.off % 4 or y.ld % 4 or y.off % 4:
+        raise ValueError("conv3x3_c64_x3: 16-byte aligned fp32 row views expected")
+    if scale.numel() < 64 or shift.numel() < 64 or ACT[act] > 1:
+        raise ValueError("conv3x3_c64_x3: affine size / activation (none or relu)")
+    wp, wps = _x3_planes(wt_planes, 64 * 576, "conv3x3_c64_x3")
+    m = n * h * w
+    xp = x.need(m, 64, "c64x3.x")
+    yp = y.need(m, 64, "c64x3.y")
+    _launch("conv", "sp_conv3x3_c64_x3", (xp, x.ld, wp, wps, scale.data_ptr(), shift.data_ptr(), yp, y.ld, n, h, w,
+                                          ACT[act], stream()),
+            2 * m * 64 * 576, 4 * (m * 64 + m * 64) + 6 * 64 * 576, (m, 64, 576, 3, 1, "x3", "direct"))
+
+
+def conv3x3_c32_x3(x: V, wt_planes: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, y: V, n: int, h: int,
+                   w: int, cout: int, act=None):
+    """Stem convs 2 / 3 (Cin 32 → Cout 32 or 64) of the fp32 path on dense fp32 rows and the hi / mid / lo weight
+    planes: the direct LDS-halo kernel sp_conv3x3_c32_x3, bit-identical to conv2d(..., wt_planes=...)."""
+    if x.is_bf16 or y.is_bf16 or x.ld != 32 or y.ld != cout or x.off % 4 or y.off % 4 or cout not in (32, 64):
+        raise ValueError("conv3x3_c32_x3: dense fp32 rows (ld 32 in, Cout 32 or 64 out) expected")
+    if scale.numel() < cout or shift.numel() < cout or ACT[act] > 1:
+        raise ValueError("conv3x3_c32_x3: affine size / activation (none or relu)")
+    wp, wps = _x3_planes(wt_planes, cout * 288, "conv3x3_c32_x3")
+    m = n * h * w
+    xp = x.need(m, 32, "c32x3.x")
+    yp = y.need(m, cout, "c32x3.y")
+    _launch("conv", "sp_conv3x3_c32_x3", (xp, wp, wps, scale.data_ptr(), shift.data_ptr(), yp, n, h, w, cout,
+                                          ACT[act], stream()),
+            2 * m * cout * 288, 4 * (m * 32 + m * cout) + 6 * cout * 288, (m, cout, 288, 3, 1, "x3", "direct"))
+
+
 def _pool_out(y, m: int, c: int, what: str):
     """y: a dense tensor or a V row view (a channel slice of a wider buffer) → (ptr, ldy)."""
     if isinstance(y, V):

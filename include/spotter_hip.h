@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SP_ABI_VERSION 17
+#define SP_ABI_VERSION 18
 
 enum sp_act { SP_ACT_NONE = 0, SP_ACT_RELU = 1, SP_ACT_SILU = 2, SP_ACT_GELU = 3 };
 /* GEMM operand precision:
@@ -176,6 +176,32 @@ enum sp_tuning_knob {
   SP_TUNE_MSDA_GENERIC = 4,   /* ABI v14: 1 = sp_msda's per-lane kernel where the point-sharing one applies (A/B) */
 };
 int sp_set_tuning(int knob, int value);
+/* ABI v18: the kernel instantiation sp_conv2d would launch for this descriptor under the calling thread's
+ * overrides (sp_set_conv_config, sp_set_splitk_config, sp_set_tuning): sp_conv2d's argument checks and tile
+ * choice without a launch. It touches no device and dereferences no pointer of the descriptor (nullness and
+ * alignment only). Returns 0, or < 0 with the sp_last_error text sp_conv2d would give. */
+enum sp_conv_family {
+  SP_CONV_FP32 = 0,      /* conv_gemm_kernel (fp32 MFMA) */
+  SP_CONV_MFMA16 = 1,    /* conv_mfma16_kernel (register-staged, bf16 / split operands) */
+  SP_CONV_GLDS = 2,      /* conv_glds_kernel (LDS-DMA) */
+  SP_CONV_PIPE = 3,      /* diagnostic builds: conv_pipe_kernel */
+  SP_CONV_PP = 4,        /* diagnostic builds: conv_pp_kernel */
+  SP_CONV_X3S = 5,       /* diagnostic builds: conv_x3s_kernel */
+  SP_CONV_X3P = 6,       /* diagnostic builds: conv_x3p_kernel */
+  SP_CONV_FUSED_LN = 7,  /* diagnostic builds: conv_gemm_kernel with the row-LayerNorm epilogue */
+};
+typedef struct {
+  int32_t family;    /* sp_conv_family */
+  int32_t tile;      /* the tile's public id (sp_set_conv_config: 221, 4, 46, ...; never 100+id / 200+id) */
+  int32_t planes;    /* operand planes: 0 fp32, 1 bf16, 3 the 3-way split */
+  int32_t generic;   /* 1: generic gather (Cin % 32 != 0 or unaligned operands), 0: the fast operand path */
+  int32_t a_bf16;    /* 1: the bf16-A-rows form of the tile */
+  int32_t fast_1x1;  /* 1: the LDS-DMA kernels' 1x1 fast path (V = 2) */
+  int32_t epilogue;  /* LDS-DMA epilogue variant 1-4 (1: the plain one, and every other family) */
+  int32_t splits;    /* split-K factor (1: none) */
+  int32_t counters;  /* 1: split-K combined in the launch (arrival counters), 0: the reduce launch */
+} sp_conv_plan_info;
+int sp_conv_plan(const sp_conv_desc* d, sp_conv_plan_info* out);
 
 /* 3x3 stride-1 pad-1 convolution by Winograd F(2x2, 3x3) (ABI v9): the same result contract as
  * sp_conv2d on the same descriptor (KH = KW = 3, stride 1, pad 1; act, scale / shift, res1 / res2 as

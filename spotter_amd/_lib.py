@@ -13,7 +13,7 @@ import threading
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPOTTER_HIP_LIB", os.path.join(HERE, "libspotter_hip.so"))
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -46,6 +46,11 @@ class SpConvDesc(C.Structure):
         ("C_bf16", vp), ("res1_bf16", vp), ("res2_bf16", vp),
         ("splitk_counters", vp), ("splitk_counters_len", i64),
     ]
+
+
+class SpConvPlanInfo(C.Structure):
+    _fields_ = [(f, i32) for f in ("family", "tile", "planes", "generic", "a_bf16", "fast_1x1", "epilogue", "splits",
+                                   "counters")]
 
 
 class SpMsdaDesc(C.Structure):
@@ -118,6 +123,7 @@ _SIGS = {
     "sp_set_conv_config": (i32, [i32]),
     "sp_set_splitk_config": (i32, [i32, i32, i32]),
     "sp_set_tuning": (i32, [i32, i32]),
+    "sp_conv_plan": (i32, [C.POINTER(SpConvDesc), C.POINTER(SpConvPlanInfo)]),
     "sp_conv3x3_winograd": (i32, [C.POINTER(SpConvDesc), vp, i64, vp, i64, vp]),
     "sp_winograd_f23_input": (i32, [C.POINTER(SpConvDesc), vp, i64, vp]),
     "sp_winograd_f23_gemm": (i32, [C.POINTER(SpConvDesc), vp, i64, vp, i64, vp]),

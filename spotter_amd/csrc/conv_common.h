@@ -36,7 +36,8 @@ struct ConvArgs {
   const uint16_t* A16 = nullptr;
   int64_t a_plane_stride = 0;
   // split-K with the in-launch combine (splitk_combine): one arrival counter per output tile (set by the
-  // launchers whose kernels call splitk_combine, from sp_conv_desc.splitk_counters); null: the reduce launch
+  // launchers whose kernels call splitk_combine, from sp_conv_desc.splitk_counters, where the plan says so);
+  // null: the reduce launch
   int32_t* counters = nullptr;
 };
 
@@ -144,7 +145,7 @@ __device__ __forceinline__ void epilogue_store(const ConvArgs& p, int64_t m, int
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// A buffer descriptor over the split-K partial slabs (offsets below 2^31 bytes: splitk_counters_for).
+// A buffer descriptor over the split-K partial slabs (offsets below 2^31 bytes: plan_conv takes the counters only then).
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t partial_rsrc(const ConvArgs& p) {
   return __builtin_amdgcn_make_buffer_rsrc(p.partial, 0, 0x7fffffff, 0x00020000);
 }
@@ -262,16 +263,6 @@ __device__ __forceinline__ void epilogue_tile(const ConvArgs& p, float* region, 
       }
     }
   }
-}
-
-// The counters a split-K launch of `tiles` output tiles may use: the descriptor's array when it has one
-// entry per tile (and the partial slabs are addressable by 32-bit buffer offsets, at most 16 splits), else
-// null (the separate reduce launch).
-inline int32_t* splitk_counters_for(const ConvArgs& a, int64_t tiles) {
-  return (a.splits > 1 && a.splits <= 16 && a.d.splitk_counters && tiles <= a.d.splitk_counters_len &&
-          (int64_t)a.splits * a.M * a.ldp * 4 < (int64_t(1) << 31))
-             ? a.d.splitk_counters
-             : nullptr;
 }
 
 // In-launch split-K combine (ABI v13), called by every workgroup of a split-K launch with counters after its
@@ -399,16 +390,6 @@ __device__ __forceinline__ void epilogue_rowln(const ConvArgs& p, float* tile, c
   }
 }
 
-// conv_mfma16.hip: bf16-operand MFMA GEMM (planes = 1: bf16; planes = 3: fp32 via a 3-way bf16
-// split). cfg < 0 picks the tile by shape. Returns 0 or the launch error.
-int launch_mfma16(const ConvArgs& a, int planes, int cfg, hipStream_t s);
-// The LDS-DMA tile configurations of launch_mfma16 (conv_glds.hip); -2 when cfg is not one of them.
-int launch_glds_cfg(const ConvArgs& a, int planes, int cfg, hipStream_t s);
-// Tuning: the split mode's slab-epilogue form for the calling thread (4 = direct stores, else the slab
-// store pass; sp_set_tuning SP_TUNE_GLDS_EPILOGUE).
-void set_glds_epilogue(int v);
-// The tile configuration sp_set_conv_config forced for the calling thread (-1: none).
-int forced_cfg();
 // Split-K combine kernel launch (conv_gemm.hip).
 int launch_splitk_reduce(const ConvArgs& a, hipStream_t s);
 

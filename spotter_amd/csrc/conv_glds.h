@@ -1,6 +1,7 @@
 // LDS-DMA implicit-GEMM kernel templates on bf16-operand MFMA (x3 split / bf16): the tile
-// configurations 11-65 of launch_mfma16 (conv_mfma16.hip), instantiated by conv_glds_p*.hip.
+// configurations of SP_GLDS_CONFIGS (conv_plan.h), instantiated by conv_glds_p*.hip.
 #pragma once
+#include "conv_plan.h"
 #include "mfma16_common.h"
 
 #ifndef SP_ABLATE
@@ -43,33 +44,6 @@ __device__ unsigned long long g_glds_stamps[16384 * 6];
 #endif
 
 namespace {
-
-template <int WM, int WN, int TM, int TN, int PL, int NS, int BK, int APL = 0>
-struct GldsCfg {
-  // (64-deep stages were built and measured at 0.70-0.92x of the same wave tile at k32 for both operand
-  // modes, profiles/r3/bf16/ab_bk64_*.jsonl: the larger stages cost workgroups per CU; removed in round 4)
-  static_assert(BK == 32 || BK == 16, "k per stage");
-  static constexpr int NT = 64 * WM * WN;
-  static constexpr int BM = 32 * TM * WM;
-  static constexpr int BN = 32 * TN * WN;
-  // APL: A in memory — 0: fp32 A, split / rounded per fragment; 1: bf16 rows (ConvArgs::A16, bf16 mode)
-  static_assert(APL == 0 || APL == PL, "bf16 A planes match the operand mode");
-  static constexpr int RA = APL ? BK / 8 : BK / 4;  // 16-byte chunks per A row of one plane
-  static constexpr int RB = BK / 8;  // 16-byte chunks per bf16 B row (4 / 2)
-  static constexpr int CAP = BM * RA;  // 16-byte chunks of one A plane
-  static constexpr int CA = CAP * (APL ? APL : 1);  // ... of the whole A stage
-  static constexpr int CB = BN * RB;  // 16-byte chunks of one bf16 B plane
-  static constexpr int GAP = CAP / NT;  // DMA pieces per thread per A plane
-  static constexpr int GA = CA / NT;
-  static constexpr int GB = CB / NT;
-  static_assert(GAP * NT == CAP && GB * NT == CB && GB >= 1 && GAP >= 1, "DMA pieces must tile the workgroup");
-  static constexpr int GLDS = GA + PL * GB;  // DMA instructions per thread per stage
-  static constexpr int STAGE = CA + PL * CB;
-  static constexpr int NB = (WM * WN * TM * 32 * TN * 32 / 4 <= NS * STAGE) ? TM : 1;
-  static constexpr int EPI = WM * WN * NB * 32 * TN * 32 / 4;
-  static constexpr int SMEM = NS * STAGE > EPI ? NS * STAGE : EPI;
-  static_assert(NS >= 2 && NS <= 6, "stages");
-};
 
 // The LDS-DMA main loop of one output tile: k-tiles [kt0, kt1) of tile `wg` (N fastest) accumulated
 // into acc (acc4 for 16x16x32 MFMAs). The caller zeroes the accumulators and owns the epilogue.
@@ -665,7 +639,7 @@ __device__ __forceinline__ void glds_epilogue(const ConvArgs& p, uint4* smem, in
         for (int q = 0; q < 16; ++q) acc[i][j][q] = acc4[2 * i + (q >> 3)][2 * j + ((q >> 2) & 1)][q & 3];
   }
   float* region = smemf + wave * (C::NB * 32 * TN * 32);
-  // EPV 2 kernels carry only the residual-DMA epilogue (launch_glds checks its conditions on the host): a
+  // EPV 2 kernels carry only the residual-DMA epilogue (plan_glds checks its conditions on the host): a
   // runtime choice between the two made hipcc read all accumulators out of the AGPRs ahead of the branch
   if constexpr (EPV == 2)
     epilogue_tile_rd<TM, TN, C::NB, M16>(p, region, acc, m0 + wm * TM * 32, n0 + wn * TN * 32, lane);
@@ -678,7 +652,7 @@ __device__ __forceinline__ void glds_epilogue(const ConvArgs& p, uint4* smem, in
 }
 
 // OCC: minimum waves per SIMD the register allocation must allow (1 = unconstrained). Applied to the
-// 1×1 fast-path instantiations only (launch_glds): the general path's extra address registers spill.
+// 1×1 fast-path instantiations only (launch_glds_tile): the general path's extra address registers spill.
 template <int WM, int WN, int TM, int TN, int PL, int NS, int BK, bool M16, int V = 1, int OCC = 1, int APL = 0,
           int EPV = 1>
 __global__ __launch_bounds__(64 * WM * WN, OCC) void conv_glds_kernel(const ConvArgs p) {
@@ -714,165 +688,71 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void conv_glds_kernel(const Conv
 #endif
 }
 
-// The 1×1 fast path (V = 2) applies: KH = KW = 1, stride 1, no padding (A row m is A + m·lda), and
-// every byte offset of a batch member's A and weight plane fits 32 bits.
-inline bool t1_ok(const ConvArgs& a) {
-  const sp_conv_desc& d = a.d;
-  return d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad == 0 && d.Ho == d.H && d.Wo == d.W &&
-         a.M * d.lda * (a.A16 ? 2 : 4) < (int64_t(1) << 32) && (int64_t)d.Cout * a.K * 2 < (int64_t(1) << 32);
-}
-
-// AB: the bf16-A-plane variants (ConvArgs::A16) are compiled for this tile.
+// Launches the instance of this tile the plan names (plan_glds chose one the tile is compiled with: kGldsTiles'
+// fits). AB: the bf16-A-plane variants (ConvArgs::A16) are compiled for this tile.
 template <int WM, int WN, int TM, int TN, int NS, int BK = 32, bool M16 = false, int OCC = 1, bool AB = false>
-int launch_glds(const ConvArgs& a, int planes, hipStream_t s, int epv = 1) {
-  if (a.d.Cin % BK || a.K % BK) {
-    set_error("sp_conv2d: LDS-DMA kernel needs Cin %% %d == 0 (Cin=%d)", BK, a.d.Cin);
-    return -1;
-  }
+int launch_glds_tile(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
   const int64_t per = ((a.M + BM - 1) / BM) * ((a.d.Cout + BN - 1) / BN);
-  const int64_t tiles = per * a.batch;
-  if (tiles > 0x7fffffff || (a.batch > 1 && a.splits > 1)) {
-    set_error("sp_conv2d: %lld tiles exceed the grid (or split-K on a batched GEMM)", (long long)tiles);
-    return -1;
-  }
-  // a tile whose stages do not fit the 160 KB LDS for this operand mode is not instantiated
-  using C3 = GldsCfg<WM, WN, TM, TN, 3, NS, BK>;
-  using C1 = GldsCfg<WM, WN, TM, TN, 1, NS, BK>;
-  constexpr bool fit3 = C3::SMEM * 16 <= 163840, fit1 = C1::SMEM * 16 <= 163840;
-  constexpr bool fit1a = [] {  // bf16 A rows: the bf16 operand mode only (not instantiated unless AB)
-    if constexpr (AB) return GldsCfg<WM, WN, TM, TN, 1, NS, BK, 1>::SMEM * 16 <= 163840;
-    else return false;
-  }();
-  const bool a16 = a.A16 != nullptr;
-  if (a16 && (planes == 3 || !fit1a)) return -2;  // no bf16-A form of this tile: the caller picks another
-  if ((planes == 3 && !fit3) || (planes != 3 && !(a16 ? fit1a : fit1))) {
-    set_error("sp_conv2d: tile configuration not built for %d operand plane(s)%s (LDS or bf16-A variant)", planes,
-              a16 ? " with bf16 A planes" : "");
-    return -1;
-  }
   ConvArgs ab = a;
   ab.tiles_per_batch = (int32_t)per;
-  dim3 grid((unsigned)tiles, 1, a.splits);
-  // the 1×1 fast path where it applies, else the general implicit GEMM
-  const bool t1 = t1_ok(a);
-  const dim3 blk(64 * WM * WN);
-  // the slab epilogues: fp32 rows (2: res1 fp32 or none) or bf16 rows (3: C_bf16, res1_bf16 or none, no res2);
-  // float4 epilogue, no split-K / row_scale
-  if (epv >= 2) {
-    const sp_conv_desc& d = a.d;
-    const bool base = a.vec_epi && a.splits == 1 && !d.row_scale;
-    const bool f32ok = base && !d.C_bf16 && !d.res1_bf16 && !d.res2_bf16;
-    const bool bf16ok = base && d.C_bf16 && !d.res1 && !d.res2 && !d.res2_bf16 &&
-                        (!d.res1_bf16 || ((reinterpret_cast<uintptr_t>(d.res1_bf16) & 15) == 0 && d.ldr1 % 8 == 0));
-    // variant 4 (direct stores) on request (epv 4), where its extra conditions hold; else variant 2
-    const bool f32dd = f32ok && !d.res2 && d.out_rows_per_group <= 0 &&
-                       ((a.M - 1) * d.ldc + d.Cout) * 4 < (int64_t(1) << 31) - 4;
-    epv = (epv == 4 && f32dd) ? 4 : f32ok ? 2 : bf16ok ? 3 : 1;
-  }
+  const dim3 grid((unsigned)(per * a.batch), 1, p.splits), blk(64 * WM * WN);
+  // a tile whose stages do not fit the 160 KB LDS for an operand mode is not instantiated for it
+  constexpr bool fit3 = GldsCfg<WM, WN, TM, TN, 3, NS, BK>::SMEM * 16 <= 163840;
+  constexpr bool fit1 = GldsCfg<WM, WN, TM, TN, 1, NS, BK>::SMEM * 16 <= 163840;
+  constexpr bool fit1a = glds_fit1a<WM, WN, TM, TN, NS, BK, AB>();
+  const bool x3 = p.planes == 3, a16 = p.a_bf16, t1 = p.fast_1x1;
+  const int epv = p.epilogue;
   if constexpr (fit3) {
-    if (planes == 3 && !a16 && t1 && epv == 4)
+    if (x3 && !a16 && t1 && epv == 4)
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 3, NS, BK, M16, 2, OCC, 0, 4>), grid, blk, 0, s, ab);
-    else if (planes == 3 && !a16 && t1 && epv == 2)
+    else if (x3 && !a16 && t1 && epv == 2)
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 3, NS, BK, M16, 2, OCC, 0, 2>), grid, blk, 0, s, ab);
-    else if (planes == 3 && !a16 && t1)
+    else if (x3 && !a16 && t1)
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 3, NS, BK, M16, 2, OCC>), grid, blk, 0, s, ab);
-    else if (planes == 3 && !a16)
+    else if (x3 && !a16)
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 3, NS, BK, M16, 1>), grid, blk, 0, s, ab);
   }
   if constexpr (fit1) {
-    if (planes != 3 && !a16 && t1)
+    if (!x3 && !a16 && t1)
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 2, OCC>), grid, blk, 0, s, ab);
-    else if (planes != 3 && !a16)
+    else if (!x3 && !a16)
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 1>), grid, blk, 0, s, ab);
   }
   if constexpr (fit1a) {
-    if (planes != 3 && a16 && t1 && epv == 3)
+    if (!x3 && a16 && t1 && epv == 3)
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 2, OCC, 1, 3>), grid, blk, 0, s, ab);
-    else if (planes != 3 && a16 && t1)
+    else if (!x3 && a16 && t1)
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 2, OCC, 1>), grid, blk, 0, s, ab);
-    else if (planes != 3 && a16 && epv == 3)
+    else if (!x3 && a16 && epv == 3)
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 1, 1, 1, 3>), grid, blk, 0, s, ab);
-    else if (planes != 3 && a16)
+    else if (!x3 && a16)
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 1, 1, 1>), grid, blk, 0, s, ab);
   }
-  int rc = check_launch(planes == 3 ? "sp_conv2d(f32x3 glds)" : "sp_conv2d(bf16 glds)");
-  if (rc || a.splits == 1) return rc;
+  int rc = check_launch(x3 ? "sp_conv2d(f32x3 glds)" : "sp_conv2d(bf16 glds)");
+  if (rc || p.splits == 1) return rc;
   return launch_splitk_reduce(a, s);
 }
 
-
-// The LDS-DMA tile configurations: (id, WM, WN, TM, TN, NS, BK, M16, OCC, AB). Tile BM × BN = 32·TM·WM ×
-// 32·TN·WN, WM × WN waves, NS stages of BK-deep k, M16: v_mfma_f32_16x16x32_bf16 blocks, OCC: the
-// register budget of the 1×1 fast path (waves per SIMD), AB: bf16-A-plane variants compiled.
-#define SP_GLDS_CONFIGS(X)              \
-  X(11, 2, 2, 2, 2, 3, 32, false, 1, false)    \
-  X(12, 4, 2, 2, 2, 2, 32, false, 1, true)    \
-  X(13, 2, 2, 1, 2, 3, 32, false, 1, true)    \
-  X(14, 2, 2, 1, 1, 3, 32, false, 1, true)    \
-  X(15, 2, 4, 2, 2, 2, 32, false, 1, false)    \
-  X(16, 2, 2, 2, 1, 3, 32, false, 1, true)    /* 128×64, 3 stages */ \
-  X(17, 4, 1, 2, 4, 2, 32, false, 1, false)    /* 256×128, 4 waves of 64×128 */ \
-  X(18, 2, 2, 2, 4, 2, 32, false, 1, false)    /* 128×256, 4 waves of 64×128 */ \
-  X(19, 2, 1, 2, 4, 2, 32, false, 1, false)    /* 128×128, 2 waves of 64×128, 2 stages */ \
-  X(20, 2, 1, 2, 4, 3, 32, false, 1, false)    /* 128×128, 2 waves of 64×128 */ \
-  X(33, 4, 2, 2, 4, 2, 32, false, 1, true)    /* 256×256, 8 waves of 64×128 */ \
-  X(34, 2, 4, 4, 2, 2, 32, false, 1, false)    /* 256×256, 8 waves of 128×64 */ \
-  X(35, 4, 1, 2, 4, 4, 16, false, 1, false)    /* 256×128, k16 × 4 stages */ \
-  X(36, 4, 1, 2, 4, 5, 16, false, 1, false)    /* 256×128, k16 × 5 stages */ \
-  X(37, 4, 2, 2, 4, 3, 16, false, 1, false)    /* 256×256, k16 × 3 */ \
-  X(38, 4, 2, 2, 4, 4, 16, false, 1, false)    /* 256×256, k16 × 4 */ \
-  X(41, 4, 2, 2, 2, 2, 32, true, 1, true)     /* cfg 12 on 16x16x32 MFMAs */ \
-  X(42, 4, 2, 2, 4, 2, 32, true, 1, true)     /* cfg 33 on 16x16x32 MFMAs */ \
-  X(43, 2, 2, 2, 2, 3, 32, true, 1, false)     /* cfg 11 on 16x16x32 MFMAs */ \
-  X(44, 4, 1, 2, 4, 2, 16, false, 1, true)    /* 256×128, 4 waves of 64×128, k16 × 2 */ \
-  X(45, 2, 2, 2, 2, 2, 32, false, 1, true)    /* 128×128, k32 × 2 */ \
-  X(46, 2, 2, 2, 2, 2, 16, false, 4, true)    /* 128×128, k16 × 2, four workgroups per CU (see below) */ \
-  X(47, 2, 2, 2, 2, 2, 32, true, 1, true)     /* cfg 45 on 16x16x32 MFMAs */ \
-  X(48, 2, 2, 2, 4, 2, 16, false, 1, false)    /* 128×256, 4 waves of 64×128, k16 × 2 */ \
-  X(49, 4, 1, 2, 4, 2, 32, true, 1, false)     /* cfg 17 on 16x16x32 MFMAs */ \
-  X(50, 4, 1, 2, 2, 3, 32, false, 1, false)    /* 256×64, k32 × 3 */ \
-  X(51, 4, 1, 2, 2, 2, 32, false, 1, true)    /* 256×64, k32 × 2 */ \
-  X(62, 4, 1, 1, 8, 2, 32, false, 1, false)    /* 128×256, 4 waves of 32×256 */ \
-  X(63, 8, 1, 1, 4, 2, 32, false, 1, true)    /* 256×128, 8 waves of 32×128 */ \
-  X(64, 4, 1, 1, 4, 3, 32, false, 1, true)    /* 128×128, 4 waves of 32×128, 3 stages */ \
-  X(65, 8, 1, 1, 4, 2, 32, true, 1, false)     /* cfg 63 on 16x16x32 MFMAs */ \
-  /* round 4, bf16-row candidates (deeper DMA pipelines; x3 stages do not fit at 256 rows) */ \
-  X(52, 4, 2, 2, 2, 3, 32, false, 1, true)    /* 256×128, k32 × 3 */ \
-  X(53, 4, 2, 2, 2, 3, 32, true, 1, true)     /* cfg 52 on 16x16x32 MFMAs */ \
-  X(54, 4, 2, 2, 2, 4, 32, true, 1, true)     /* 256×128, k32 × 4, 16x16x32 */ \
-  X(55, 4, 2, 2, 4, 3, 32, true, 1, true)     /* 256×256, k32 × 3, 16x16x32 */ \
-  X(56, 2, 2, 2, 2, 4, 32, true, 1, true)     /* 128×128, k32 × 4, 16x16x32 */
-// (round 5 also built 256×256 bf16-row tiles with 4 and 5 stages of 32 KB at one workgroup per CU, for the
-// long-K 3x3s: 1.1-2.3× slower than the table's tiles on all 35 C3 / C2-bf16 shapes above 0.3 ms per step,
-// 0.71 against 0.61 ms even at 102400×512×4608, profiles/r5/bf16/retune_*_256x256.json. Removed.)
-// (round 5 built 224-row tiles — 224×256 with four waves of 224×64, its 16x16x32 form, 224×128 with two
-// waves — so the 51200-row C2 GEMMs would fill the 256 CUs in one wave of 229 tiles: 1.2-2.3× slower than
-// the table's tiles on all ten 51200-row shapes, profiles/r5/x3/tune_224.json; one wave per SIMD and the
-// A split repeated by every wave cost more than the full wave of CUs gains. Removed.)
-// cfg 46's OCC = 4: registers for 4 waves per SIMD (four workgroups per CU): bit-identical, 1.02-1.09x
-// over the unconstrained allocation (3 per SIMD) on the short-K shapes it serves
-// (profiles/r3/x3/ab_glds_occupancy.jsonl); 122 VGPRs, no spill, on the 1×1 fast path (the general path
-// would spill: it keeps the unconstrained allocation).
-
 // The configurations are compiled in kGldsParts translation units (conv_glds_p<k>.hip: id % kGldsParts
-// == k) so the build runs them in parallel; launch_glds_cfg (conv_glds.hip) dispatches.
+// == k) so the build runs them in parallel; launch_glds (conv_glds.hip) dispatches on the plan's tile.
 constexpr int kGldsParts = 6;
 
 template <int PART>
-int glds_part(const ConvArgs& a, int planes, int cfg, hipStream_t s, int epv) {
-  switch (cfg) {
-#define SP_GLDS_CASE(id, WM, WN, TM, TN, NS, BK, M16, OCC, AB)                          \
-  case id:                                                                            \
-    if constexpr ((id) % kGldsParts == PART)                                          \
-      return launch_glds<WM, WN, TM, TN, NS, BK, M16, OCC, AB>(a, planes, s, epv);        \
-    else                                                                              \
-      return -2;
+int glds_part(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  switch (p.tile) {
+#define SP_GLDS_CASE(id, WM, WN, TM, TN, NS, BK, M16, OCC, AB)                     \
+  case id:                                                                       \
+    if constexpr ((id) % kGldsParts == PART)                                     \
+      return launch_glds_tile<WM, WN, TM, TN, NS, BK, M16, OCC, AB>(a, p, s);    \
+    break;
     SP_GLDS_CONFIGS(SP_GLDS_CASE)
 #undef SP_GLDS_CASE
     default:
-      return -2;
+      break;
   }
+  set_error("sp_conv2d: plan names LDS-DMA tile %d, which is not in part %d", p.tile, PART);
+  return -1;
 }
 
 }  // namespace

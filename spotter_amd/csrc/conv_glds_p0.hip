@@ -4,8 +4,8 @@
 
 #if !(SP_GLDS_STAMP || SP_GLDS_ONE_UNIT)
 namespace sp {
-int launch_glds_part0(const ConvArgs& a, int planes, int cfg, hipStream_t s, int epv) {
-  return glds_part<0>(a, planes, cfg, s, epv);
+int launch_glds_part0(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  return glds_part<0>(a, p, s);
 }
 }  // namespace sp
 #endif

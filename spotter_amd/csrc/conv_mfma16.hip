@@ -32,6 +32,7 @@
 
 #include <type_traits>
 
+#include "conv_plan.h"
 #include "mfma16_common.h"
 
 #ifndef SP_ABLATE
@@ -1359,167 +1360,71 @@ int launch_x3p(const ConvArgs& a, int planes, hipStream_t s) {
 #endif  // SP_DIAG_KERNELS (x3s / x3p)
 
 template <int WM, int WN, int TM, int TN>
-int launch_cfg(const ConvArgs& a, int planes, hipStream_t s) {
+int launch_cfg(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
   const int64_t tiles = ((a.M + BM - 1) / BM) * ((a.d.Cout + BN - 1) / BN);
-  if (tiles > 0x7fffffff) {
-    set_error("sp_conv2d: %lld tiles exceed the grid", (long long)tiles);
-    return -1;
-  }
-  dim3 grid((unsigned)tiles, 1, a.splits);
+  dim3 grid((unsigned)tiles, 1, p.splits);
   ConvArgs b = a;
-  b.counters = splitk_counters_for(a, tiles);
-  if (b.counters && planes == 3)
+  b.counters = p.counters ? a.d.splitk_counters : nullptr;
+  if (p.counters && p.planes == 3)
     hipLaunchKernelGGL((conv_mfma16_kernel<WM, WN, TM, TN, 3, true, true>), grid, dim3(64 * WM * WN), 0, s, b);
-  else if (b.counters)
+  else if (p.counters)
     hipLaunchKernelGGL((conv_mfma16_kernel<WM, WN, TM, TN, 1, true, true>), grid, dim3(64 * WM * WN), 0, s, b);
-  else if (planes == 3)
+  else if (p.planes == 3)
     hipLaunchKernelGGL((conv_mfma16_kernel<WM, WN, TM, TN, 3, true>), grid, dim3(64 * WM * WN), 0, s, b);
   else
     hipLaunchKernelGGL((conv_mfma16_kernel<WM, WN, TM, TN, 1, true>), grid, dim3(64 * WM * WN), 0, s, b);
-  int rc = check_launch(planes == 3 ? "sp_conv2d(f32x3)" : "sp_conv2d(bf16)");
-  if (rc || a.splits == 1 || b.counters) return rc;
+  int rc = check_launch(p.planes == 3 ? "sp_conv2d(f32x3)" : "sp_conv2d(bf16)");
+  if (rc || p.splits == 1 || p.counters) return rc;
+  return launch_splitk_reduce(a, s);
+}
+
+// generic gather: one small-tile instance per operand mode
+int launch_generic(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  const int64_t tiles = ((a.M + 63) / 64) * ((a.d.Cout + 63) / 64);
+  dim3 grid((unsigned)tiles, 1, p.splits);
+  if (p.planes == 3)
+    hipLaunchKernelGGL((conv_mfma16_kernel<2, 2, 1, 1, 3, false>), grid, dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((conv_mfma16_kernel<2, 2, 1, 1, 1, false>), grid, dim3(256), 0, s, a);
+  int rc = check_launch(p.planes == 3 ? "sp_conv2d(f32x3 generic)" : "sp_conv2d(bf16 generic)");
+  if (rc || p.splits == 1) return rc;
   return launch_splitk_reduce(a, s);
 }
 
 }  // namespace
 
-// cfg (register-staged kernel): 1 = 128×128 (2×2 waves of 64×64), 2 = 256×128 (4×2 waves),
-// 3 = 64×128, 4 = 64×64, 5 = 128×256 (2×4 waves), 6 = 128×64;
-// cfg (LDS-DMA kernel, no A2): 11 = 128×128 3 stages, 12 = 256×128 2 stages, 13 = 64×128 3 stages,
-// 14 = 64×64 3 stages, 15 = 128×256 2 stages, 16 = 128×64 3 stages; < 0 = by shape.
-thread_local int g_glds_epv = -1;
-void set_glds_epilogue(int v) { g_glds_epv = v; }
+bool conv_mfma16_has_diag() { return SP_DIAG_KERNELS != 0; }
 
-int launch_mfma16(const ConvArgs& a, int planes, int cfg, hipStream_t s) {
-  if (a.A16) {  // bf16 A planes: the LDS-DMA tiles only (the forced / table tile, else the by-shape rule's)
-    // bf16 output rows (the bf16 variant's maps): the slab epilogue ("+ 100" → variant 3: res1 by LDS-DMA,
-    // rounded outputs staged as bf16 quads), bit-identical, 1.0-2.1x on every tile measured
-    // (profiles/r3/bf16/ab_slab_epilogue_bf16_rows.jsonl; launch_glds falls back where it does not apply)
-    const int ep = (planes == 1 && a.d.C_bf16) ? 100 : 0;
-    if (cfg >= 11) {
-      const int rc = launch_glds_cfg(a, planes, cfg < 100 ? cfg + ep : cfg, s);
-      if (rc != -2) return rc;
-    }
-    int c = -1;
-    const auto tiles = [&](int bm, int bn) { return ((a.M + bm - 1) / bm) * ((a.d.Cout + bn - 1) / bn); };
-    if (a.d.Cout <= 64) c = tiles(128, 64) >= 192 ? 16 : 14;
-    // 3×3s on bf16 rows: 256×128 on 16x16x32 MFMAs beat 256×256 by 1.2-1.3× (profiles/r4/bf16/)
-    else if (a.d.KH == 3 && a.d.Cout % 128 == 0 && tiles(256, 128) >= 192) c = 41;
-    else if (a.d.Cout % 256 == 0 && a.K >= 512 && tiles(256, 256) >= 192) c = 33;
-    else if (a.d.Cout % 128 == 0 && tiles(128, 128) >= 192) c = planes == 3 ? 46 : 45;
-    else if (tiles(256, 128) >= 192) c = 12;
-    else if (tiles(64, 128) >= 192) c = 13;
-    else c = 14;
-    const int rc = launch_glds_cfg(a, planes, c + ep, s);
-    if (rc == -2) {
-      set_error("sp_conv2d: no LDS-DMA tile for bf16 A planes");
-      return -1;
-    }
-    return rc;
-  }
-  if (!a.fast) {  // generic gather: one small-tile instance per operand mode
-    const int64_t tiles = ((a.M + 63) / 64) * ((a.d.Cout + 63) / 64);
-    dim3 grid((unsigned)tiles, 1, a.splits);
-    if (planes == 3)
-      hipLaunchKernelGGL((conv_mfma16_kernel<2, 2, 1, 1, 3, false>), grid, dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL((conv_mfma16_kernel<2, 2, 1, 1, 1, false>), grid, dim3(256), 0, s, a);
-    int rc = check_launch(planes == 3 ? "sp_conv2d(f32x3 generic)" : "sp_conv2d(bf16 generic)");
-    if (rc || a.splits == 1) return rc;
-    return launch_splitk_reduce(a, s);
-  }
+// The register-staged tiles (ids 1-6, conv_plan.h) and, in diagnostic builds, the conv_pipe / conv_pp / conv_x3s / conv_x3p families above.
+int launch_mfma16(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
 #if SP_DIAG_KERNELS
-  if (cfg >= 70 && cfg <= 75 && (a.d.C_bf16 || a.d.res1_bf16 || a.d.res2_bf16)) cfg = -1;  // register epilogues: fp32 rows only
-  if (cfg >= 73 && cfg <= 75 && !a.d.A2 && a.splits == 1 && a.vec_epi) {
-    switch (cfg) {
-      case 73: return launch_x3p<8>(a, planes, s);  // 256×256 persistent
-      case 74: return launch_x3p<6>(a, planes, s);  // 256×192 persistent
-      default: return launch_x3p<4>(a, planes, s);  // 256×128 persistent
+  if (p.family != SP_CONV_MFMA16) switch (p.tile) {
+      case 21: return launch_pipe<2, 2, 2, 2, 4>(a, p.planes, s);  // 128×128, 4 stages
+      case 22: return launch_pipe<2, 2, 2, 4, 3>(a, p.planes, s);  // 128×256 (wave 64×128)
+      case 23: return launch_pipe<4, 1, 2, 4, 3>(a, p.planes, s);  // 256×128 (wave 64×128)
+      case 24: return launch_pipe<2, 2, 2, 2, 3>(a, p.planes, s);  // 128×128, 3 stages
+      case 25: return launch_pipe<4, 2, 2, 2, 3>(a, p.planes, s);  // 256×128, 8 waves
+      case 26: return launch_pipe<2, 2, 2, 1, 4>(a, p.planes, s);  // 128×64, 4 stages
+      case 31: return launch_pp<2, 2>(a, p.planes, s);  // 256×128, waves of 64×64
+      case 32: return launch_pp<1, 2>(a, p.planes, s);  // 128×128, waves of 32×64
+      case 70: return launch_x3s<8>(a, p.planes, s);  // 256×256
+      case 71: return launch_x3s<6>(a, p.planes, s);  // 256×192
+      case 72: return launch_x3s<4>(a, p.planes, s);  // 256×128
+      case 73: return launch_x3p<8>(a, p.planes, s);  // 256×256 persistent
+      case 74: return launch_x3p<6>(a, p.planes, s);  // 256×192 persistent
+      case 75: return launch_x3p<4>(a, p.planes, s);  // 256×128 persistent
+      default: break;
     }
-  }
-  if (cfg >= 70 && cfg <= 72 && !a.d.A2) {
-    switch (cfg) {
-      case 70: return launch_x3s<8>(a, planes, s);  // 256×256
-      case 71: return launch_x3s<6>(a, planes, s);  // 256×192
-      default: return launch_x3s<4>(a, planes, s);  // 256×128
-    }
-  }
-#else
-  if (cfg >= 70 && cfg <= 75 && !a.d.A2) {
-    set_error("sp_conv2d: tile configuration %d (conv_x3s / conv_x3p) is in the diagnostic build only", cfg);
-    return -1;
-  }
 #endif
-#if SP_DIAG_KERNELS
-  if (cfg >= 31 && cfg <= 32 && !a.d.A2) {
-    switch (cfg) {
-      case 31: return launch_pp<2, 2>(a, planes, s);  // 256×128, waves of 64×64
-      default: return launch_pp<1, 2>(a, planes, s);  // 128×128, waves of 32×64
-    }
-  }
-  if (cfg >= 21 && cfg <= 26 && !a.d.A2) {
-    switch (cfg) {
-      case 21: return launch_pipe<2, 2, 2, 2, 4>(a, planes, s);   // 128×128, 4 stages
-      case 22: return launch_pipe<2, 2, 2, 4, 3>(a, planes, s);   // 128×256 (wave 64×128)
-      case 23: return launch_pipe<4, 1, 2, 4, 3>(a, planes, s);   // 256×128 (wave 64×128)
-      case 24: return launch_pipe<2, 2, 2, 2, 3>(a, planes, s);   // 128×128, 3 stages
-      case 25: return launch_pipe<4, 2, 2, 2, 3>(a, planes, s);   // 256×128, 8 waves
-      default: return launch_pipe<2, 2, 2, 1, 4>(a, planes, s);   // 128×64, 4 stages
-    }
-  }
-#else
-  if (((cfg >= 31 && cfg <= 32) || (cfg >= 21 && cfg <= 26)) && !a.d.A2) {
-    set_error("sp_conv2d: tile configuration %d (conv_pipe / conv_pp) is in the diagnostic build only", cfg);
-    return -1;
-  }
-#endif
-  // The slab epilogue (conv_glds.h epilogue_tile_rd, "cfg + 100") on the split mode's launches with a BN affine
-  // or a residual, for the tiles where it measured faster, bit-identical either way: 1.02-1.28x on the
-  // bottleneck expands (the res1 band fetched by LDS-DMA; profiles/r3/x3/ab_residual_dma_epilogue.jsonl),
-  // 1.02-1.19x without a residual (the BN constants hoisted per lane; ab_slab_epilogue_nores.jsonl) on tiles
-  // 12, 14, 41, 45, 46, 47, 63, 64; 0.59-0.96x on the 256-wide-N / TN = 4 four-wave tiles (33, 44)
-  if (planes == 3 && !a.A16 && (a.d.res1 || a.d.scale || a.d.shift) && !a.d.row_scale && a.vec_epi &&
-      a.splits == 1 && !a.d.C_bf16 &&
-      (cfg == 12 || cfg == 14 || cfg == 41 || cfg == 45 || cfg == 46 || cfg == 47 || cfg == 63 || cfg == 64))
-    cfg += g_glds_epv == 4 ? 200 : 100;
-  // cfg + 100: the LDS-DMA residual epilogue variant; cfg + 200: its direct-store form
-  const int gc = cfg >= 211 && cfg <= 265 ? cfg - 200 : cfg >= 111 && cfg <= 165 ? cfg - 100 : cfg;
-  if (((gc >= 11 && gc <= 20) || (gc >= 33 && gc <= 38) || (gc >= 41 && gc <= 51) || (gc >= 62 && gc <= 65)) && !a.d.A2) {
-    const int rc = launch_glds_cfg(a, planes, cfg, s);
-    if (rc != -2) return rc;
-  }
-  if (cfg < 0 || (cfg > 6 && cfg < 11) || (cfg > 26 && cfg < 31) || (cfg > 38 && cfg < 41) || (cfg > 51 && cfg < 62) || (cfg > 65 && cfg < 70) || (cfg > 75 && gc == cfg) || (cfg >= 73 && cfg <= 75 && (a.splits > 1 || !a.vec_epi)) || (cfg >= 11 && a.d.A2)) {
-    // By shape (tools/conv_bench.py sweeps): the LDS-DMA kernel whenever the operands allow it,
-    // the largest tile that still gives >= 192 workgroups, a 64-wide N tile for Cout <= 64;
-    // 256×256 where Cout is a multiple of 256 and K >= 512 (+10-16 % there; a 384-wide N wastes
-    // half of its second column of tiles, and at K = 256 the 256×128 tile stays ahead).
-    const auto tiles = [&](int bm, int bn) { return ((a.M + bm - 1) / bm) * ((a.d.Cout + bn - 1) / bn); };
-    const bool dma = !a.d.A2;
-    // f32x3, measured (profiles/r1/conv_sweep_2wg_x3.jsonl): short-K wide-N layers (the K = 128 / 256
-    // bottleneck expands, the decoder value projection) and 384 / 128-wide outputs on mid-size grids
-    // run best with two workgroups per CU (LDS <= 80 KB), where one workgroup's prologue and residual
-    // epilogue overlap the other's MFMAs: 1.32× on the stage-3 expand, 1.10× on the CCFM 3×3 @ 40².
-    const bool x3 = planes == 3;
-    if (a.splits > 1) cfg = 4;
-    else if (dma && x3 && a.K <= 256 && a.d.Cout >= 512 && tiles(128, 128) >= 192) cfg = 46;
-    else if (dma && x3 && a.d.Cout % 128 == 0 && a.d.Cout % 256 != 0 && a.M >= 40000 &&
-             (a.M < 150000 || a.d.Cout == 128) && tiles(128, 128) >= 192) cfg = 45;
-    else if (a.d.Cout <= 64)
-      cfg = dma ? (x3 && a.d.Cout == 64 && tiles(256, 64) >= 192 ? 51 : (tiles(128, 64) >= 192 ? 16 : 14)) : 4;
-    else if (dma && a.d.Cout % 256 == 0 && a.K >= 512 && tiles(256, 256) >= 192) cfg = 33;
-    else if (tiles(256, 128) >= 192) cfg = dma ? (a.M >= 150000 ? 41 : 12) : 2;  // tall M: 16x16x32 +6 %
-    else if (tiles(64, 128) >= 192) cfg = dma ? 13 : 3;
-    else cfg = dma ? 14 : 4;
-    if (cfg >= 11) return launch_mfma16(a, planes, cfg, s);
-  }
-  switch (cfg) {
-    case 1: return launch_cfg<2, 2, 2, 2>(a, planes, s);
-    case 2: return launch_cfg<4, 2, 2, 2>(a, planes, s);
-    case 3: return launch_cfg<2, 2, 1, 2>(a, planes, s);
-    case 5: return launch_cfg<2, 4, 2, 2>(a, planes, s);
-    case 6: return launch_cfg<2, 2, 2, 1>(a, planes, s);
-    default: return launch_cfg<2, 2, 1, 1>(a, planes, s);
+  if (p.generic) return launch_generic(a, p, s);
+  switch (p.tile) {
+    case 1: return launch_cfg<2, 2, 2, 2>(a, p, s);
+    case 2: return launch_cfg<4, 2, 2, 2>(a, p, s);
+    case 3: return launch_cfg<2, 2, 1, 2>(a, p, s);
+    case 5: return launch_cfg<2, 4, 2, 2>(a, p, s);
+    case 6: return launch_cfg<2, 2, 2, 1>(a, p, s);
+    default: return launch_cfg<2, 2, 1, 1>(a, p, s);
   }
 }
 

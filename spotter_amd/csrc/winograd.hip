@@ -17,6 +17,7 @@
 // per thread (24 float4 loads, 32 float4 stores), the output transform one tile (16 non-temporal
 // float4 loads, 4 float4 stores + the epilogue's residual loads).
 #include <cstdlib>
+#include "conv_plan.h"
 #include "mfma16_common.h"
 
 namespace sp {
@@ -435,7 +436,7 @@ int wino_gemm(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino, 
   // 16x16x32 MFMAs (247) for the wide batches from 400000 rows (80²×384: 1.162 vs 1.241 ms for cfg 44),
   // 128×128 k16 at four workgroups per CU (246) for Cout <= 256 (40²×256: 0.177 vs 0.184; 80²×128: 0.268 vs
   // 0.282), 128×128 k32 (245) otherwise (40²×384: 0.308 vs 0.327; 20²×512: 0.140 vs 0.150 for cfg 47).
-  int cfg = forced_cfg();
+  int cfg = conv_overrides().cfg;
   if (cfg < 0) {
     // short batches (the bs1 80² maps, 14400 rows; not the bs32 20² maps at 28800): 256×128 with eight 32×128
     // waves for Cout >= 256 (0.0395 vs 0.0535 ms for 245 at 80²×384), else 64×64 (0.0103 vs 0.0114 for 246 at
@@ -446,12 +447,9 @@ int wino_gemm(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino, 
     else if (d->Cout <= 256) cfg = 246;
     else cfg = 245;
   }
-  const int rc = launch_glds_cfg(g, planes, cfg, as_stream(stream));
-  if (rc == -2) {
-    set_error("%s: tile configuration %d is not an LDS-DMA configuration", what, cfg);
-    return -1;
-  }
-  return rc;
+  ConvPlan p;
+  if (int rc = plan_glds(g, planes, cfg, what, &p)) return rc;
+  return launch_glds(g, p, as_stream(stream));
 }
 
 template <int MT>

@@ -301,6 +301,17 @@ def force_splitk_config(cfg=None, max_splits=None, min_ktiles=None):
                                0 if min_ktiles is None else int(min_ktiles))
 
 
+def conv_plan(desc) -> dict:
+    """The kernel instantiation sp_conv2d would launch for an SpConvDesc under this thread's overrides
+    (sp_conv_plan: no device call): {"family", "tile", "planes", "generic", "a_bf16", "fast_1x1", "epilogue",
+    "splits", "counters"}. Raises with sp_conv2d's message where sp_conv2d would fail."""
+    from ._lib import SpConvPlanInfo, call
+
+    info = SpConvPlanInfo()
+    call("sp_conv_plan", C.byref(desc), C.byref(info))
+    return {f: getattr(info, f) for f, _ in SpConvPlanInfo._fields_}
+
+
 TUNE_GLDS_EPILOGUE = 3  # include/spotter_hip.h sp_tuning_knob
 
 

@@ -79,7 +79,8 @@ def test_ctypes_descriptors_match_the_header_layout(tmp_path):
     from spotter_amd import _lib
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    structs = {"sp_conv_desc": _lib.SpConvDesc, "sp_msda_desc": _lib.SpMsdaDesc}
+    structs = {"sp_conv_desc": _lib.SpConvDesc, "sp_msda_desc": _lib.SpMsdaDesc,
+               "sp_conv_plan_info": _lib.SpConvPlanInfo}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "spotter_hip.h"', "int main(void) {"]
     for cname, py in structs.items():
         lines.append(f'  printf("{cname} sizeof %zu\\n", sizeof({cname}));')
@@ -128,6 +129,43 @@ def test_arg_errors_are_reported_without_a_gpu():
     d = _lib.SpConvDesc(A=16, C=16, KH=3, KW=3, stride=2, pad=1)
     assert L.sp_conv3x3_winograd(C.byref(d), C.c_void_p(16), 0, C.c_void_p(16), 0, None) < 0
     assert b"stride-1" in L.sp_last_error()
+
+
+def test_conv_plan_matches_the_recorded_dispatch():
+    """sp_conv_plan (the planner sp_conv2d launches from) names, for every case of tests/golden/conv_plan.jsonl.gz,
+    the instantiation recorded at the launch sites of the commit before the planner existed (the fixture's first
+    line; tools/gen_conv_plan_golden.py), or gives the same error text: exact, every line, no GPU."""
+    import ctypes as C
+    import gzip
+    import json
+
+    from spotter_amd import _lib
+
+    L = _lib.load()
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "conv_plan.jsonl.gz"), "rt") as f:
+        head, *lines = [json.loads(ln) for ln in f]
+    names = [f for f, _ in _lib.SpConvDesc._fields_]
+    assert head["fields"] == names and len(lines) > 6000
+    defaults = [-1, -1, 0, 0, -1]
+    bad, desc = [], None
+    try:
+        for i, (enc, o, want) in enumerate(lines):
+            if enc != 0:
+                desc = _lib.SpConvDesc(**{names[int(k)]: v for k, v in enc.items()})
+            o = o + defaults[len(o):]
+            L.sp_set_conv_config(o[0])
+            L.sp_set_splitk_config(o[1], o[2], o[3])
+            L.sp_set_tuning(3, o[4])
+            info = _lib.SpConvPlanInfo()
+            rc = L.sp_conv_plan(C.byref(desc), C.byref(info))
+            got = [getattr(info, f) for f, _ in info._fields_] if rc == 0 else L.sp_last_error().decode()
+            if got != want:
+                bad.append((i + 2, o, want, got))
+    finally:
+        L.sp_set_conv_config(-1)
+        L.sp_set_splitk_config(-1, 0, 0)
+        L.sp_set_tuning(3, -1)
+    assert not bad, (len(bad), bad[:10])
 
 
 def test_dropin_interface_and_pickling():

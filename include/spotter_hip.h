@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SP_ABI_VERSION 18
+#define SP_ABI_VERSION 19
 
 enum sp_act { SP_ACT_NONE = 0, SP_ACT_RELU = 1, SP_ACT_SILU = 2, SP_ACT_GELU = 3 };
 /* GEMM operand precision:
@@ -44,8 +44,16 @@ enum sp_act { SP_ACT_NONE = 0, SP_ACT_RELU = 1, SP_ACT_SILU = 2, SP_ACT_GELU = 3
  *                of |a·b| (one fp32 rounding), so the result is fp32-accurate (checked against
  *                fp64 next to the fp32 MFMA path in tests/test_gpu_kernels.py).
  *                Weights from Wt_bf16 as three planes [3][Cout][K] (plane stride
- *                wt_plane_stride); activations are split while staging. */
-enum sp_precision { SP_PREC_FP32 = 0, SP_PREC_BF16 = 1, SP_PREC_F32X3 = 2 };
+ *                wt_plane_stride); activations are split while staging;
+ *  SP_PREC_F32X2 (ABI v19) the TF32-class tier: fp32 operands as 2-way bf16 splits x = hi + lo + rho with
+ *                hi = RNE(x), lo = RNE(x - hi), so |x - hi| <= 2^-8 |x| and |rho| <= 2^-16 |x| (about 16
+ *                significand bits kept); products lo·hi + hi·lo + hi·hi (smallest first) on bf16 MFMA with fp32
+ *                accumulate. The dropped lo·lo, rho_a·b and a·rho_b sum to <= 3·2^-16 |a·b| (1 + 2^-7) per
+ *                product: 256x tighter than SP_PREC_BF16, about 10 bits looser than SP_PREC_F32X3, for half of
+ *                SP_PREC_F32X3's MFMAs. Weights from Wt_bf16 as two planes [2][Cout][K] (plane stride
+ *                wt_plane_stride); activations and outputs stay fp32 rows; every argument check is
+ *                SP_PREC_F32X3's with two planes. */
+enum sp_precision { SP_PREC_FP32 = 0, SP_PREC_BF16 = 1, SP_PREC_F32X3 = 2, SP_PREC_F32X2 = 3 };
 
 /* One uint8 RGB HWC image in device memory. */
 typedef struct {
@@ -86,8 +94,9 @@ typedef struct {
   int32_t out_rows_per_group; int64_t out_group_stride;
   float* workspace; int64_t workspace_elems; /* optional fp32 scratch enabling split-K (small M) */
   int32_t precision;         /* sp_precision */
-  const uint16_t* Wt_bf16;   /* [Cout][K] bf16 weights (SP_PREC_BF16), [3][Cout][K] (SP_PREC_F32X3) */
-  int64_t wt_plane_stride;   /* elements between the hi / mid / lo planes (SP_PREC_F32X3) */
+  const uint16_t* Wt_bf16;   /* [Cout][K] bf16 weights (SP_PREC_BF16), [3][Cout][K] (SP_PREC_F32X3),
+                              * [2][Cout][K] (SP_PREC_F32X2) */
+  int64_t wt_plane_stride;   /* elements between the hi / mid / lo (SP_PREC_F32X3) or hi / lo (SP_PREC_F32X2) planes */
   /* Optional row LayerNorm fused into the epilogue (ABI v8): when ln_gamma is set,
    *   out[m, :] = LayerNorm(acc·row_scale·scale + shift + res1)[m, :] · ln_gamma + ln_beta   (eps ln_eps)
    * over the whole output row — the post-norm "Linear → +residual → LayerNorm" of the AIFI and decoder
@@ -193,7 +202,7 @@ enum sp_conv_family {
 typedef struct {
   int32_t family;    /* sp_conv_family */
   int32_t tile;      /* the tile's public id (sp_set_conv_config: 221, 4, 46, ...; never 100+id / 200+id) */
-  int32_t planes;    /* operand planes: 0 fp32, 1 bf16, 3 the 3-way split */
+  int32_t planes;    /* operand planes: 0 fp32, 1 bf16, 2 the 2-way split (SP_PREC_F32X2), 3 the 3-way split */
   int32_t generic;   /* 1: generic gather (Cin % 32 != 0 or unaligned operands), 0: the fast operand path */
   int32_t a_bf16;    /* 1: the bf16-A-rows form of the tile */
   int32_t fast_1x1;  /* 1: the LDS-DMA kernels' 1x1 fast path (V = 2) */
@@ -207,11 +216,11 @@ int sp_conv_plan(const sp_conv_desc* d, sp_conv_plan_info* out);
  * sp_conv2d on the same descriptor (KH = KW = 3, stride 1, pad 1; act, scale / shift, res1 / res2 as
  * above; no A2, row_scale, grouped rows or LayerNorm; Cin % 32 == 0, Cout % 4 == 0, 16-byte aligned
  * operands), computed as input transform V = B^T d B per 2x2 output tile → 16 batched GEMMs
- * V_ab · U_ab on the split (SP_PREC_F32X3) or bf16 (SP_PREC_BF16) MFMA kernels → output transform
+ * V_ab · U_ab on the split (SP_PREC_F32X3 / SP_PREC_F32X2) or bf16 (SP_PREC_BF16) MFMA kernels → output transform
  * Y = A^T M A + the fused epilogue. 2.25x fewer GEMM multiply-adds than the implicit GEMM; fp32 error
  * on par with the direct fp32 conv. wt_wino: the transformed weights U = G g G^T (computed in fp64 on
  * the host, rounded to fp32) as bf16 planes [planes][16][Cout][Cin] (component ab = 4a + b), planes
- * wino_plane_stride elements apart (3 planes for SP_PREC_F32X3, 1 for SP_PREC_BF16); d->Wt /
+ * wino_plane_stride elements apart (3 planes for SP_PREC_F32X3, 2 for SP_PREC_F32X2, 1 for SP_PREC_BF16); d->Wt /
  * d->Wt_bf16 are not read. work: fp32 scratch of >= 16 * T * (Cin + Cout) elements,
  * T = N * ceil(H/2) * ceil(W/2). Replaces sp_conv2d for the RepVGG 3x3 (M2:921-923) and other
  * stride-1 3x3 convs (M2:817-835, RN:78-103). */

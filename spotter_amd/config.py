@@ -120,6 +120,7 @@ PRESETS = {"r101vd": R101VD, "r18vd": R18VD}
 PRECISIONS = {
     "fp32": ("x3", "x3"),
     "fp32-mfma": ("f32", "f32"),
+    "fp32-x2": ("x2", "x2"),  # the TF32-class tier: 2-way bf16 split, three products (SP_PREC_F32X2)
     "bf16": ("bf16", "bf16"),
     "bf16-convs": ("bf16", "x3"),
     "bf16-all": ("bf16", "bf16"),  # round-2 name of "bf16"

@@ -1,4 +1,4 @@
-// LDS-DMA implicit-GEMM kernel templates on bf16-operand MFMA (x3 split / bf16): the tile
+// LDS-DMA implicit-GEMM kernel templates on bf16-operand MFMA (x3 / x2 split / bf16): the tile
 // configurations of SP_GLDS_CONFIGS (conv_plan.h), instantiated by conv_glds_p*.hip.
 #pragma once
 #include "conv_plan.h"
@@ -690,7 +690,9 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void conv_glds_kernel(const Conv
 
 // Launches the instance of this tile the plan names (plan_glds chose one the tile is compiled with: kGldsTiles'
 // fits). AB: the bf16-A-plane variants (ConvArgs::A16) are compiled for this tile.
-template <int WM, int WN, int TM, int TN, int NS, int BK = 32, bool M16 = false, int OCC = 1, bool AB = false>
+// X2: the 2-way split (PL = 2) forms are compiled for this tile (GldsTile::fit2).
+template <int WM, int WN, int TM, int TN, int NS, int BK = 32, bool M16 = false, int OCC = 1, bool AB = false,
+          bool X2 = false>
 int launch_glds_tile(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
   const int64_t per = ((a.M + BM - 1) / BM) * ((a.d.Cout + BN - 1) / BN);
@@ -701,8 +703,21 @@ int launch_glds_tile(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   constexpr bool fit3 = GldsCfg<WM, WN, TM, TN, 3, NS, BK>::SMEM * 16 <= 163840;
   constexpr bool fit1 = GldsCfg<WM, WN, TM, TN, 1, NS, BK>::SMEM * 16 <= 163840;
   constexpr bool fit1a = glds_fit1a<WM, WN, TM, TN, NS, BK, AB>();
-  const bool x3 = p.planes == 3, a16 = p.a_bf16, t1 = p.fast_1x1;
+  const bool x3 = p.planes == 3, x2 = p.planes == 2, a16 = p.a_bf16, t1 = p.fast_1x1;
   const int epv = p.epilogue;
+  if constexpr (X2) {  // the split mode's four forms on two planes
+    if (x2 && !a16 && t1 && epv == 4)
+      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 2, NS, BK, M16, 2, OCC, 0, 4>), grid, blk, 0, s, ab);
+    else if (x2 && !a16 && t1 && epv == 2)
+      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 2, NS, BK, M16, 2, OCC, 0, 2>), grid, blk, 0, s, ab);
+    else if (x2 && !a16 && t1)
+      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 2, NS, BK, M16, 2, OCC>), grid, blk, 0, s, ab);
+    else if (x2 && !a16)
+      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 2, NS, BK, M16, 1>), grid, blk, 0, s, ab);
+  } else if (x2) {
+    set_error("sp_conv2d: LDS-DMA tile %d is not built for two operand planes", p.tile);
+    return -1;
+  }
   if constexpr (fit3) {
     if (x3 && !a16 && t1 && epv == 4)
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 3, NS, BK, M16, 2, OCC, 0, 4>), grid, blk, 0, s, ab);
@@ -714,9 +729,9 @@ int launch_glds_tile(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 3, NS, BK, M16, 1>), grid, blk, 0, s, ab);
   }
   if constexpr (fit1) {
-    if (!x3 && !a16 && t1)
+    if (!x3 && !x2 && !a16 && t1)
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 2, OCC>), grid, blk, 0, s, ab);
-    else if (!x3 && !a16)
+    else if (!x3 && !x2 && !a16)
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 1>), grid, blk, 0, s, ab);
   }
   if constexpr (fit1a) {
@@ -729,7 +744,7 @@ int launch_glds_tile(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
     else if (!x3 && a16)
       hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 1, 1, 1>), grid, blk, 0, s, ab);
   }
-  int rc = check_launch(x3 ? "sp_conv2d(f32x3 glds)" : "sp_conv2d(bf16 glds)");
+  int rc = check_launch(x3 ? "sp_conv2d(f32x3 glds)" : x2 ? "sp_conv2d(f32x2 glds)" : "sp_conv2d(bf16 glds)");
   if (rc || p.splits == 1) return rc;
   return launch_splitk_reduce(a, s);
 }
@@ -744,7 +759,7 @@ int glds_part(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
 #define SP_GLDS_CASE(id, WM, WN, TM, TN, NS, BK, M16, OCC, AB)                     \
   case id:                                                                       \
     if constexpr ((id) % kGldsParts == PART)                                     \
-      return launch_glds_tile<WM, WN, TM, TN, NS, BK, M16, OCC, AB>(a, p, s);    \
+      return launch_glds_tile<WM, WN, TM, TN, NS, BK, M16, OCC, AB, glds_tile(id)->fit2>(a, p, s); \
     break;
     SP_GLDS_CONFIGS(SP_GLDS_CASE)
 #undef SP_GLDS_CASE

@@ -14,6 +14,10 @@
 //           accumulator is rounded 6 times per 16 k here versus 16 times for the fp32 MFMA
 //           (v_mfma_f32_32x32x2_f32 ≡ an fmaf chain), so the result is fp32-accurate while the
 //           matrix core runs 6 × 32 = 192 cycles per 32×32×16 block instead of 8 × 64 = 512.
+//   PL = 2  TF32-class fp32 via a 2-way split (SP_PREC_F32X2): x = hi + lo + ρ with hi = bf16(x),
+//           lo = bf16(x - hi), |ρ| <= 2^-16 |x|, and the three products lo·hi, hi·lo, hi·hi (smallest
+//           first). The dropped lo·lo, ρ_a·b and a·ρ_b sum to <= 3·2^-16 |a b| (1 + 2^-7) per product:
+//           256× tighter than one bf16 plane, half the MFMAs and 24 instead of 44 split VALU per 8 elements.
 //
 // Same GEMM contract and fused epilogue as conv_gemm.hip (conv_common.h): A gathered on the fly
 // from NHWC activations (implicit im2col), W as [Cout][K] bf16 planes (k contiguous).
@@ -460,9 +464,9 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_pipe_kernel(const ConvArgs 
       for (int j = 0; j < TN; ++j) acc[i][j] = mfma_planes<PL>(fa[i], fb[j], acc[i][j]);
   };
   // per MFMA of the current step: first the next step's ds_reads (2 per gap), then its VALU
-  constexpr int NMF = TM * TN * (PL == 3 ? 6 : 1);
+  constexpr int NMF = TM * TN * plane_products(PL);
   constexpr int NDS = TM * 2 + TN * PL;
-  constexpr int NVALU = TM * (PL == 3 ? 48 : 8) + 8;
+  constexpr int NVALU = TM * (PL == 3 ? 48 : PL == 2 ? 24 : 8) + 8;
   constexpr int VSTART = NMF > 4 ? 2 : 1;
   constexpr int VPER = (NVALU + (NMF - VSTART) - 1) / (NMF - VSTART > 0 ? NMF - VSTART : 1);
   auto interleave = [&]() {
@@ -549,7 +553,7 @@ int launch_pipe(const ConvArgs& a, int planes, hipStream_t s) {
 // Ping-pong LDS-DMA kernel: 8 waves as two groups of four (waves 0-3 = group A, 4-7 = group B; a
 // workgroup's waves land on the 4 SIMDs in turn, so every SIMD holds one wave of each group). Per
 // k-tile a wave runs a MEMORY phase (fragment ds_reads + the fp32→bf16-plane split, and for group A
-// the LDS-DMA issue of the next k-tile) and a COMPUTE phase (its TM·TN·(PL==3 ? 6 : 1)·2 MFMAs),
+// the LDS-DMA issue of the next k-tile) and a COMPUTE phase (its TM·TN·plane_products(PL)·2 MFMAs),
 // each ended by a workgroup barrier. Group B starts one phase late, so on every SIMD one wave's
 // MFMA chain runs while the other wave does its loads and split VALU: the matrix pipe no longer
 // waits for the operand work (the glds kernel measured that work and the MFMAs as additive).
@@ -1226,7 +1230,7 @@ __global__ __launch_bounds__(512) void conv_x3p_kernel(const ConvArgs p, int nti
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       if (j + 1 < TN) __builtin_amdgcn_sched_group_barrier(0x100, PL, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, PL == 3 ? 6 : 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, plane_products(PL), 0);
     }
   };
   // fused epilogue straight from the Cᵀ accumulators: lane (r, h) of block j holds pixel m0 + 32·wave + r,
@@ -1368,13 +1372,17 @@ int launch_cfg(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   b.counters = p.counters ? a.d.splitk_counters : nullptr;
   if (p.counters && p.planes == 3)
     hipLaunchKernelGGL((conv_mfma16_kernel<WM, WN, TM, TN, 3, true, true>), grid, dim3(64 * WM * WN), 0, s, b);
+  else if (p.counters && p.planes == 2)
+    hipLaunchKernelGGL((conv_mfma16_kernel<WM, WN, TM, TN, 2, true, true>), grid, dim3(64 * WM * WN), 0, s, b);
   else if (p.counters)
     hipLaunchKernelGGL((conv_mfma16_kernel<WM, WN, TM, TN, 1, true, true>), grid, dim3(64 * WM * WN), 0, s, b);
   else if (p.planes == 3)
     hipLaunchKernelGGL((conv_mfma16_kernel<WM, WN, TM, TN, 3, true>), grid, dim3(64 * WM * WN), 0, s, b);
+  else if (p.planes == 2)
+    hipLaunchKernelGGL((conv_mfma16_kernel<WM, WN, TM, TN, 2, true>), grid, dim3(64 * WM * WN), 0, s, b);
   else
     hipLaunchKernelGGL((conv_mfma16_kernel<WM, WN, TM, TN, 1, true>), grid, dim3(64 * WM * WN), 0, s, b);
-  int rc = check_launch(p.planes == 3 ? "sp_conv2d(f32x3)" : "sp_conv2d(bf16)");
+  int rc = check_launch(p.planes == 3 ? "sp_conv2d(f32x3)" : p.planes == 2 ? "sp_conv2d(f32x2)" : "sp_conv2d(bf16)");
   if (rc || p.splits == 1 || p.counters) return rc;
   return launch_splitk_reduce(a, s);
 }
@@ -1385,9 +1393,13 @@ int launch_generic(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   dim3 grid((unsigned)tiles, 1, p.splits);
   if (p.planes == 3)
     hipLaunchKernelGGL((conv_mfma16_kernel<2, 2, 1, 1, 3, false>), grid, dim3(256), 0, s, a);
+  else if (p.planes == 2)
+    hipLaunchKernelGGL((conv_mfma16_kernel<2, 2, 1, 1, 2, false>), grid, dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL((conv_mfma16_kernel<2, 2, 1, 1, 1, false>), grid, dim3(256), 0, s, a);
-  int rc = check_launch(p.planes == 3 ? "sp_conv2d(f32x3 generic)" : "sp_conv2d(bf16 generic)");
+  int rc = check_launch(p.planes == 3   ? "sp_conv2d(f32x3 generic)"
+                        : p.planes == 2 ? "sp_conv2d(f32x2 generic)"
+                                        : "sp_conv2d(bf16 generic)");
   if (rc || p.splits == 1) return rc;
   return launch_splitk_reduce(a, s);
 }

@@ -23,9 +23,10 @@
 //   70-72               conv_x3s   (diagnostic)       | (conv_mfma16.hip); an error in the product library
 //   73-75               conv_x3p   (diagnostic)      /
 //
-// With bf16 / split operands (planes 1 / 3) a forced id is read as id, 100+id or 200+id only, so the fp32
+// With bf16 / split operands (planes 1 / 2 / 3) a forced id is read as id, 100+id or 200+id only, so the fp32
 // digit codes mean something else there (220 = 200+20); with fp32 operands only the eighteen digit codes are
-// ids. An id that cannot apply falls back to the by-shape rule (plan_conv says where).
+// ids. An id that cannot apply falls back to the by-shape rule (plan_conv says where); with the 2-way split
+// (planes 2) that includes every LDS-DMA id outside kGldsX2Ids.
 #pragma once
 
 #include "conv_common.h"
@@ -47,7 +48,7 @@ struct ConvOverrides {
 const ConvOverrides& conv_overrides();
 
 // sp_conv2d's argument checks and the derived launch arguments (M, K, fast, vec_epi, split-K factor):
-// 0, or -1 with the error set. `planes`: 0 fp32, 1 bf16, 3 the split.
+// 0, or -1 with the error set. `planes`: 0 fp32, 1 bf16, 2 the 2-way split, 3 the 3-way split.
 int conv_args(const sp_conv_desc* d, const ConvOverrides& o, ConvArgs* a, int* planes);
 // The planner: a pure function of its arguments (no HIP call; of the descriptor's pointers it reads only
 // nullness and alignment). 0, or -1 with the error set.
@@ -154,11 +155,18 @@ constexpr int kGldsSlabIds[] = {12, 14, 41, 45, 46, 47, 63, 64};
 // The round-4 bf16-row candidates: taken as a forced / table id with bf16 A rows only (with fp32 A rows
 // sp_conv2d falls back by shape; the Winograd GEMMs take them).
 constexpr int kGldsBf16AOnlyIds[] = {52, 53, 54, 55, 56};
+// The tiles compiled for the 2-way split (SP_PREC_F32X2, PL = 2): the ids the 3-way split mode reaches — the
+// by-shape rule of plan_conv (12 13 14 16 33 41 45 46 51), the Winograd rule (winograd.hip: 14 45 46 47 63) and
+// the split-operand entries of tile_table.h (14 33 44 45 46 47 63 64) — so the new mode starts from the split
+// mode's tile for every shape without instantiating all of SP_GLDS_CONFIGS a third time. With two planes any
+// other forced / tabled id falls back to the by-shape rule, as inapplicable ids do.
+constexpr int kGldsX2Ids[] = {12, 13, 14, 16, 33, 41, 44, 45, 46, 47, 51, 63, 64};
 
 struct GldsTile {
   int id, BM, BN, BK;
   bool fit3, fit1, fit1a;  // the stages fit the 160 KB LDS: split operands, bf16 operands, bf16 A rows (AB tiles)
   bool slab, a16_only;     // in kGldsSlabIds / kGldsBf16AOnlyIds
+  bool fit2;               // built for the 2-way split: in kGldsX2Ids and its stages fit the LDS
 };
 template <int N>
 constexpr bool id_in(const int (&set)[N], int id) {
@@ -175,7 +183,8 @@ constexpr GldsTile kGldsTiles[] = {
 #define SP_GLDS_TILE(id, WM, WN, TM, TN, NS, BK, M16, OCC, AB)                                                   \
   {id, 32 * TM * WM, 32 * TN * WN, BK, GldsCfg<WM, WN, TM, TN, 3, NS, BK>::SMEM * 16 <= 163840,                  \
    GldsCfg<WM, WN, TM, TN, 1, NS, BK>::SMEM * 16 <= 163840, glds_fit1a<WM, WN, TM, TN, NS, BK, AB>(),            \
-   id_in(kGldsSlabIds, id), id_in(kGldsBf16AOnlyIds, id)},
+   id_in(kGldsSlabIds, id), id_in(kGldsBf16AOnlyIds, id),                                                        \
+   id_in(kGldsX2Ids, id) && GldsCfg<WM, WN, TM, TN, 2, NS, BK>::SMEM * 16 <= 163840},
     SP_GLDS_CONFIGS(SP_GLDS_TILE)
 #undef SP_GLDS_TILE
 };

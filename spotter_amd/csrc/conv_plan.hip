@@ -54,7 +54,8 @@ int plan_glds_tile(const ConvArgs& a, int planes, const GldsTile& t, int req, Co
     return -1;
   }
   const bool a16 = a.A16 != nullptr;
-  if ((planes == 3 && !t.fit3) || (planes != 3 && !(a16 ? t.fit1a : t.fit1))) {
+  if ((planes == 3 && !t.fit3) || (planes == 2 && (a16 || !t.fit2)) ||
+      (planes < 2 && !(a16 ? t.fit1a : t.fit1))) {
     set_error("sp_conv2d: tile configuration not built for %d operand plane(s)%s (LDS or bf16-A variant)", planes,
               a16 ? " with bf16 A planes" : "");
     return -1;
@@ -77,10 +78,10 @@ int plan_glds_tile(const ConvArgs& a, int planes, const GldsTile& t, int req, Co
   p->generic = 0;
   p->a_bf16 = a16;
   p->fast_1x1 = t1_ok(a);
-  // the instances compiled: variants 2 / 4 for split operands on the 1×1 fast path, 3 for bf16 A rows; every
-  // other combination runs the plain epilogue
+  // the instances compiled: variants 2 / 4 for split operands (two or three planes) on the 1×1 fast path, 3 for
+  // bf16 A rows; every other combination runs the plain epilogue
   if (a16) p->epilogue = epv == 3 ? 3 : 1;
-  else p->epilogue = (planes == 3 && p->fast_1x1 && (epv == 2 || epv == 4)) ? epv : 1;
+  else p->epilogue = (planes >= 2 && p->fast_1x1 && (epv == 2 || epv == 4)) ? epv : 1;
   p->counters = 0;
   return 0;
 }
@@ -107,14 +108,17 @@ int conv_args(const sp_conv_desc* d, const ConvOverrides& o, ConvArgs* out, int*
   SP_ARG_CHECK(d->act >= 0 && d->act <= 3, "sp_conv2d: bad act %d", d->act);
   SP_ARG_CHECK(!d->row_scale || d->row_period > 0, "sp_conv2d: row_period");
   SP_ARG_CHECK(d->precision == SP_PREC_FP32 || d->precision == SP_PREC_BF16 ||
-                   d->precision == SP_PREC_F32X3,
+                   d->precision == SP_PREC_F32X3 || d->precision == SP_PREC_F32X2,
                "sp_conv2d: precision %d", d->precision);
-  const int planes = d->precision == SP_PREC_BF16 ? 1 : d->precision == SP_PREC_F32X3 ? 3 : 0;
+  const int planes = d->precision == SP_PREC_BF16    ? 1
+                     : d->precision == SP_PREC_F32X3 ? 3
+                     : d->precision == SP_PREC_F32X2 ? 2
+                                                     : 0;
   SP_ARG_CHECK(!(d->C_bf16 || d->res1_bf16 || d->res2_bf16) || planes == 1,
                "sp_conv2d: bf16 output / residual rows need the bf16 operand mode (SP_PREC_BF16)");
   SP_ARG_CHECK(planes == 0 || d->Wt_bf16, "sp_conv2d: bf16 / split precision needs Wt_bf16");
   const int64_t K = (int64_t)d->KH * d->KW * d->Cin;
-  SP_ARG_CHECK(planes < 3 || d->wt_plane_stride >= (int64_t)d->Cout * K,
+  SP_ARG_CHECK(planes < 2 || d->wt_plane_stride >= (int64_t)d->Cout * K,
                "sp_conv2d: wt_plane_stride %lld < Cout*K", (long long)d->wt_plane_stride);
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   if (d->A_bf16) {
@@ -197,9 +201,12 @@ int plan_conv(const ConvArgs& a, int planes, const ConvOverrides& o, ConvPlan* p
     p->tile = 1101 + 10 * (d.Cout / 128);  // 1×4 waves of 32 × 32·TN, TN = Cout / 128: 1111 … 1141
     return 0;
   }
-  // tile choice: a test / tuning override, else the measured exact-shape table (tile_table.h), else by shape
+  // tile choice: a test / tuning override, else the measured exact-shape table (tile_table.h), else by shape.
+  // The 2-way split (planes 2) has no measurements of its own yet: it takes every choice the 3-way split takes
+  // for the same descriptor (the table key, the by-shape rule, the slab epilogue), sp: "split operands".
+  const bool sp = planes >= 2;
   int cfg = o.cfg;
-  if (cfg < 0 && a.splits == 1) cfg = tile_table_lookup(a.M, d.Cout, a.K, d.KH, d.stride, planes);
+  if (cfg < 0 && a.splits == 1) cfg = tile_table_lookup(a.M, d.Cout, a.K, d.KH, d.stride, sp ? 3 : planes);
   if (cfg < 0 && a.splits > 1 && planes && o.splitk_cfg >= 0) cfg = o.splitk_cfg;
 
   if (planes == 0) {  // ---- fp32 MFMA
@@ -234,6 +241,14 @@ int plan_conv(const ConvArgs& a, int planes, const ConvOverrides& o, ConvPlan* p
   int id, req;
   decode_cfg(cfg, &id, &req);
   const GldsTile* t = glds_tile(id);
+  // two planes: an LDS-DMA tile outside kGldsX2Ids, or an id of the diagnostic families (built for one and three
+  // planes), is no id: it falls back by shape, where every tile the rule names is in the set
+  if (planes == 2 && ((t && !t->a16_only && !t->fit2) || (req == 1 && id >= 21 && id <= 32) ||
+                      (req == 1 && id >= 70 && id <= 75))) {
+    id = -1;
+    req = 1;
+    t = nullptr;
+  }
 
   if (a.A16) {  // bf16 A rows: the LDS-DMA tiles with a bf16-A form only
     // bf16 output rows (the bf16 variant's maps) request the slab epilogue (variant 3: res1 by LDS-DMA, rounded
@@ -316,7 +331,7 @@ int plan_conv(const ConvArgs& a, int planes, const ConvOverrides& o, ConvPlan* p
     // bottleneck expands, the decoder value projection) and 384 / 128-wide outputs on mid-size grids
     // run best with two workgroups per CU (LDS <= 80 KB), where one workgroup's prologue and residual
     // epilogue overlap the other's MFMAs: 1.32× on the stage-3 expand, 1.10× on the CCFM 3×3 @ 40².
-    const bool x3 = planes == 3;
+    const bool x3 = sp;
     if (a.splits > 1) id = 4;
     else if (dma && x3 && a.K <= 256 && d.Cout >= 512 && tiles(128, 128) >= 192) id = 46;
     else if (dma && x3 && d.Cout % 128 == 0 && d.Cout % 256 != 0 && a.M >= 40000 &&
@@ -334,7 +349,7 @@ int plan_conv(const ConvArgs& a, int planes, const ConvOverrides& o, ConvPlan* p
   if (t) {
     // The slab epilogue on the split mode's launches with a BN affine or a residual, for the tiles where it
     // measured faster (kGldsSlabIds), whether the id was forced, tabled or chosen by shape
-    if (req == 1 && t->slab && planes == 3 && (d.res1 || d.scale || d.shift) && !d.row_scale && a.vec_epi &&
+    if (req == 1 && t->slab && sp && (d.res1 || d.scale || d.shift) && !d.row_scale && a.vec_epi &&
         a.splits == 1 && !d.C_bf16)
       req = o.glds_epv == 4 ? 4 : 2;
     return plan_glds_tile(a, planes, *t, req, p);

@@ -1,5 +1,5 @@
 // Pieces shared by the bf16-operand MFMA GEMM kernels (conv_mfma16.hip, conv_glds.hip): the bf16 /
-// 3-way split operand forms, the six-product MFMA sums and the LDS-DMA primitives.
+// 2-way / 3-way split operand forms, the three- and six-product MFMA sums and the LDS-DMA primitives.
 #pragma once
 
 #include "conv_common.h"
@@ -13,31 +13,42 @@ constexpr int KT = 32;  // k per LDS stage
 
 __device__ __forceinline__ int sw16(int row, int c) { return row * 4 + (c ^ ((row >> 2) & 3)); }
 
-// 8 fp32 → PL bf16 planes (RNE). PL = 3: exact residual chain hi / mid / lo.
+// MFMAs per accumulator block and k step of a PL-plane operand mode: 1 (bf16), 3 (the 2-way split: hi·hi +
+// hi·lo + lo·hi), 6 (the 3-way split).
+constexpr int plane_products(int pl) { return pl == 3 ? 6 : pl == 2 ? 3 : 1; }
+
+// 8 fp32 → PL bf16 planes (RNE). PL = 3: exact residual chain hi / mid / lo; PL = 2: hi and lo = RNE(x - hi)
+// (the residual x - hi - lo, <= 2^-16 |x|, is dropped).
 template <int PL>
 __device__ __forceinline__ void split8(const float4& x0, const float4& x1, bf16x8* out) {
+  static_assert(PL >= 1 && PL <= 3, "operand planes");
   const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
   bf16x8 h, m, l;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     h[j] = (__bf16)v[j];
-    if constexpr (PL == 3) {
+    if constexpr (PL >= 2) {
       const float r1 = v[j] - (float)h[j];
       m[j] = (__bf16)r1;
-      const float r2 = r1 - (float)m[j];
-      l[j] = (__bf16)r2;
+      if constexpr (PL == 3) {
+        const float r2 = r1 - (float)m[j];
+        l[j] = (__bf16)r2;
+      }
     }
   }
   out[0] = h;
-  if constexpr (PL == 3) {
-    out[1] = m;
-    out[2] = l;
-  }
+  if constexpr (PL >= 2) out[1] = m;
+  if constexpr (PL == 3) out[2] = l;
 }
 
 template <int PL>
 __device__ __forceinline__ f32x16 mfma_planes(const bf16x8* a, const bf16x8* b, f32x16 acc) {
+  static_assert(PL >= 1 && PL <= 3, "operand planes");
   if constexpr (PL == 1) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
+  } else if constexpr (PL == 2) {  // the six-product chain below without its a[2] / b[2] and a[1]·b[1] terms
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
   } else {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc, 0, 0, 0);
@@ -54,7 +65,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // Same six-product sum on v_mfma_f32_16x16x32_bf16 (one 16×16 block, k = 32 per instruction).
 template <int PL>
 __device__ __forceinline__ f32x4 mfma16x16_planes(const bf16x8* a, const bf16x8* b, f32x4 acc) {
+  static_assert(PL >= 1 && PL <= 3, "operand planes");
   if constexpr (PL == 1) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], acc, 0, 0, 0);
+  } else if constexpr (PL == 2) {  // the six-product chain below without its a[2] / b[2] and a[1]·b[1] terms
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], acc, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], acc, 0, 0, 0);
   } else {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], acc, 0, 0, 0);
@@ -92,6 +108,7 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
 // v_cvt_pk_bf16_f32, 8 + 8 unpacks (the low half of a pair is `u << 16`, the high half `u &
 // 0xffff0000`: bf16 → fp32 is exact) and 16 v_sub_f32 — 44 instructions, against ~60 for the
 // element-wise form (hipcc converts element by element, then repacks). Same RNE hi / mid / lo as split8.
+// PL = 2 stops after the first residual: 8 v_cvt_pk_bf16_f32, 8 unpacks and 8 v_sub_f32 — 24 instructions.
 // Round 5 built the residual subtractions as packed pairs (f32x2 arithmetic → v_pk_add_f32: 36 VALU per 8
 // elements instead of 44, bit-identical); it measured 0.3 % slower in the C2 step (same box, alternating,
 // profiles/r5/x3/ab_round5_changes.json), so the scalar form stays. -DSP_SPLIT_PK2=1: the packed form (A/B).
@@ -107,7 +124,9 @@ __device__ __forceinline__ void split_frag_pk(const float4& x0, const float4& x1
     const float a = v[2 * q], b = v[2 * q + 1];
     const uint32_t h = cvt_pk_bf16(a, b);
     H[q] = h;
-    if constexpr (PL == 3) {
+    if constexpr (PL == 2) {
+      M[q] = cvt_pk_bf16(a - __builtin_bit_cast(float, h << 16), b - __builtin_bit_cast(float, h & 0xffff0000u));
+    } else if constexpr (PL == 3) {
 #if SP_SPLIT_PK2
       const f32x2 ab = {a, b};
       const f32x2 hf = {__builtin_bit_cast(float, h << 16), __builtin_bit_cast(float, h & 0xffff0000u)};
@@ -127,10 +146,8 @@ __device__ __forceinline__ void split_frag_pk(const float4& x0, const float4& x1
     }
   }
   out[0] = __builtin_bit_cast(bf16x8, make_uint4(H[0], H[1], H[2], H[3]));
-  if constexpr (PL == 3) {
-    out[1] = __builtin_bit_cast(bf16x8, make_uint4(M[0], M[1], M[2], M[3]));
-    out[2] = __builtin_bit_cast(bf16x8, make_uint4(L[0], L[1], L[2], L[3]));
-  }
+  if constexpr (PL >= 2) out[1] = __builtin_bit_cast(bf16x8, make_uint4(M[0], M[1], M[2], M[3]));
+  if constexpr (PL == 3) out[2] = __builtin_bit_cast(bf16x8, make_uint4(L[0], L[1], L[2], L[3]));
 }
 
 template <int PL>

@@ -341,11 +341,11 @@ int wino_check(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino,
   SP_ARG_CHECK(d->N > 0 && d->H > 0 && d->W > 0, "%s: bad shape", what);
   SP_ARG_CHECK(d->Cin % 32 == 0 && d->Cout % 4 == 0 && d->Cout > 0,
                "%s: needs Cin %% 32 == 0, Cout %% 4 == 0 (Cin=%d Cout=%d)", what, d->Cin, d->Cout);
-  SP_ARG_CHECK(d->precision == SP_PREC_F32X3 || d->precision == SP_PREC_BF16,
+  SP_ARG_CHECK(d->precision == SP_PREC_F32X3 || d->precision == SP_PREC_F32X2 || d->precision == SP_PREC_BF16,
                "%s: precision %d (split or bf16 operands)", what, d->precision);
   SP_ARG_CHECK(!d->A2 && !d->row_scale && d->out_rows_per_group == 0 && !d->ln_gamma,
                "%s: A2 / row_scale / grouped rows / LayerNorm are not supported", what);
-  const int planes = d->precision == SP_PREC_BF16 ? 1 : 3;
+  const int planes = d->precision == SP_PREC_BF16 ? 1 : d->precision == SP_PREC_F32X2 ? 2 : 3;
   SP_ARG_CHECK(!need_wt || planes == 1 || wino_plane_stride >= (int64_t)NC * d->Cout * d->Cin,
                "%s: wino_plane_stride %lld < %d*Cout*Cin", what, (long long)wino_plane_stride, NC);
   SP_ARG_CHECK(d->lda % 4 == 0 && d->ldc % 4 == 0 && al16(d->A) && al16(d->C) && (!need_wt || al16(wt_wino)) &&
@@ -394,7 +394,7 @@ int wino_gemm(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino, 
   int th, tw;
   int64_t T;
   if (int rc = wino_check<MT>(what, d, wt_wino, wino_plane_stride, work, work_elems, true, &th, &tw, &T)) return rc;
-  const int planes = d->precision == SP_PREC_BF16 ? 1 : 3;
+  const int planes = d->precision == SP_PREC_BF16 ? 1 : d->precision == SP_PREC_F32X2 ? 2 : 3;
   // the NC component GEMMs as one batched launch: M = T tiles, K = Cin, no epilogue
   ConvArgs g;
   memset(&g.d, 0, sizeof(g.d));
@@ -437,6 +437,10 @@ int wino_gemm(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino, 
   // 128×128 k16 at four workgroups per CU (246) for Cout <= 256 (40²×256: 0.177 vs 0.184; 80²×128: 0.268 vs
   // 0.282), 128×128 k32 (245) otherwise (40²×384: 0.308 vs 0.327; 20²×512: 0.140 vs 0.150 for cfg 47).
   int cfg = conv_overrides().cfg;
+  if (planes == 2 && cfg >= 0) {  // a forced tile that is not built for two planes (kGldsX2Ids): by the rule below
+    const GldsTile* t = glds_tile(cfg >= 300 ? -1 : cfg % 100);
+    if (t && !t->fit2) cfg = -1;
+  }
   if (cfg < 0) {
     // short batches (the bs1 80² maps, 14400 rows; not the bs32 20² maps at 28800): 256×128 with eight 32×128
     // waves for Cout >= 256 (0.0395 vs 0.0535 ms for 245 at 80²×384), else 64×64 (0.0103 vs 0.0114 for 246 at

@@ -46,6 +46,8 @@ bf16_bits = ops.bf16_bits  # fp32 → bf16 bit patterns, RNE (host, weight-pack 
 # precision → (conv GEMM operand mode, linear GEMM operand mode):
 #   "f32"  fp32 MFMA (v_mfma_f32_32x32x2_f32, an exact fmaf chain),
 #   "x3"   fp32 operands as hi/mid/lo bf16 splits on bf16 MFMA (SP_PREC_F32X3; fp32-accurate),
+#   "x2"   fp32 operands as hi/lo bf16 splits, three products (SP_PREC_F32X2; the TF32-class tier "fp32-x2":
+#          <= 3·2^-16 |a·b| per product, fp32 maps; packed, tiled and Winograd-ed as "x3" is),
 #   "bf16" bf16 operands, fp32 accumulate (the separately reported bf16 variant).
 # (Cout, K, small_m) layers inside the thin / small-M rule above where the split kernel measured faster
 # than the fp32 MFMA at bs32 (tools/tune_conv.py --cross, profiles/r2/tune_bs32_r101vd_cross_r2.json; each
@@ -68,7 +70,7 @@ def _wkw(wq):
     """ops.conv2d keyword for a packed GEMM weight form (see Engine._wq)."""
     if wq is None:
         return {}
-    if wq.dim() == 2 and wq.shape[0] == 3:
+    if wq.dim() == 2 and wq.shape[0] in (2, 3):  # the split planes: ops.conv2d reads the mode off their count
         return {"wt_planes": wq}
     return {"wt16": wq}
 
@@ -79,7 +81,7 @@ class ConvW:
     def __init__(self, w, cin, cout, k, scale, shift, w16=None, host=None, mode="f32"):
         self.w, self.cin, self.cout, self.k, self.scale, self.shift = w, cin, cout, k, scale, shift
         self.w16 = w16
-        self.mode = mode  # operand mode of w16: "f32" (none: fp32 MFMA), "bf16" (one plane), "x3" (three)
+        self.mode = mode  # operand mode of w16: "f32" (none: fp32 MFMA), "bf16" (one plane), "x2" (two), "x3" (three)
         self.host = host  # the packed fp32 [Cout, K] weights on the host (pack-time fusions read them)
         self.wino = None  # Winograd F(2x2, 3x3) weight planes when this stride-1 3x3 runs that way
         self.x3p = None  # hi / mid / lo planes of a layer whose GEMM mode is "f32" but whose direct kernel is x3
@@ -253,25 +255,29 @@ class Engine:
     # ------------------------------------------------------------------ weights
     def _wq(self, w: np.ndarray, mode: str):
         """GEMM operand form of host fp32 weights w [Cout, K], uploaded: None (fp32 MFMA), bf16 bit
-        patterns (RNE), or the hi / mid / lo bf16 planes of the fp32-accurate split path. The
-        rounding runs in numpy at pack time; the device only receives bit patterns."""
+        patterns (RNE), the hi / mid / lo bf16 planes of the fp32-accurate split path, or the hi / lo planes
+        of the 2-way split ("x2"). The rounding runs in numpy at pack time; the device only receives bit patterns."""
         if mode == "f32":
             return None
         if mode == "bf16":
             return torch.from_numpy(bf16_bits(w).view(np.int16)).to(self.dev)
+        if mode == "x2":
+            return torch.from_numpy(ops.split_bf16x2_host(w)).to(self.dev)
         return torch.from_numpy(ops.split_bf16x3_host(w)).to(self.dev)
 
     def _add_wino(self, cw: ConvW):
         """Attach the F(2x2, 3x3) transformed weight planes (host fp64 transform, then the conv's own
-        operand form: three split planes or one bf16 plane) to a stride-1 3x3 conv the Winograd policy
+        operand form: three or two split planes, or one bf16 plane) to a stride-1 3x3 conv the Winograd policy
         (self.winograd) selects."""
         if cw.k != 3 or cw.mode == "f32" or cw.cin % 32 or cw.cout % 4 or not self.winograd:
             return cw
-        if self.winograd == "auto" and (cw.cin < (self.WINO43_MIN_CIN if self.wino_m == 4 else 256) or cw.mode != "x3"):
+        if self.winograd == "auto" and (cw.cin < (self.WINO43_MIN_CIN if self.wino_m == 4 else 256) or cw.mode not in ("x3", "x2")):
             return cw
         u = ops.winograd_weights_host(cw.host.reshape(cw.cout, 3, 3, cw.cin), self.wino_m)
         if cw.mode == "x3":
             cw.wino = torch.from_numpy(ops.split_bf16x3_host(u)).to(self.dev)
+        elif cw.mode == "x2":
+            cw.wino = torch.from_numpy(ops.split_bf16x2_host(u)).to(self.dev)
         else:
             cw.wino = torch.from_numpy(bf16_bits(u).reshape(1, -1).view(np.int16)).to(self.dev)
         return cw
@@ -284,7 +290,9 @@ class Engine:
         and from C32_MIN_PIXELS up run on the exact-product direct kernel (sp_conv3x3_c32); with
         Engine(direct_c32_x3=True) backbone() runs them on the split planes instead (ConvW.x3p, sp_conv3x3_c32_x3:
         1.49-1.59× per launch, other roundings, so off by default)."""
-        if mode == "x3" and self.precision == "fp32" and (cout <= 64 or kdim <= 64 or small_m):
+        if mode in ("x3", "x2") and self.precision in ("fp32", "fp32-x2") and (cout <= 64 or kdim <= 64 or small_m):
+            # "fp32-x2" sends the same thin layers to the exact fp32 MFMA (never less accurate than its own mode),
+            # and keeps the stage-1 3×3 64→64 in its split mode on the implicit GEMM (no two-plane direct kernel)
             if cout == 64 and kdim >= 576 and not small_m:
                 # 3×3 64→64 (stage 1) stays in the split mode: from C64_MIN_PIXELS up _cv runs it as the direct
                 # split kernel sp_conv3x3_c64_x3 (1.65× the implicit GEMM, profiles/direct_x3/); below that the

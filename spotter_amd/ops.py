@@ -15,6 +15,9 @@ import torch
 from ._lib import SpConvDesc, SpImageU8, SpMsdaDesc, call
 
 ACT = {None: 0, "none": 0, "relu": 1, "silu": 2, "gelu": 3}
+# sp_precision (include/spotter_hip.h) by the plane count of a bf16 weight tensor, and the launch hook's tag of it
+PREC_BY_PLANES = {1: 1, 3: 2, 2: 3}
+PREC_TAG = ("f32", "bf16", "x3", "x2")
 
 _hook = None
 
@@ -83,13 +86,14 @@ def conv2d(x: V, n: int, h: int, w: int, cin: int, wt: torch.Tensor, cout: int, 
     """ln = (gamma, beta, eps): LayerNorm over each output row fused into the epilogue (fp32 weights).
     wino = (planes, work[, m]): run this 3×3 stride-1 conv as Winograd F(m×m, 3×3), m = 2 (default) or 4
     (sp_winograd_f23_* / _f43_*), on the transformed weight planes (int16 [3 or 1, (m+2)²·Cout·Cin],
-    winograd_weights_host + split) with the fp32 scratch `work`; the bf16 / split operand mode follows the
-    plane count.
+    winograd_weights_host + split; 2 planes: the 2-way split) with the fp32 scratch `work`; the bf16 / split
+    operand mode follows the plane count.
     counters (int32, zeroed once by the caller, one per stream): split-K launches combine their partial sums
     inside the GEMM launch (sp_conv_desc.splitk_counters, ABI v13) instead of a second reduce launch.
     wt16 (int16 bit patterns of bf16 weights, same [Cout][K] layout) selects the bf16 MFMA path;
     wt_planes (int16 [3, Cout*K]: the hi / mid / lo bf16 split of the fp32 weights, split_bf16x3)
-    selects the fp32-accurate 3-way-split path (SP_PREC_F32X3)."""
+    selects the fp32-accurate 3-way-split path (SP_PREC_F32X3); int16 [2, Cout*K] (hi / lo, split_bf16x2) the
+    TF32-class 2-way split (SP_PREC_F32X2)."""
     ho = (h + 2 * pad - k) // stride + 1
     wo = (w + 2 * pad - k) // stride + 1
     m = n * ho * wo
@@ -154,10 +158,10 @@ def conv2d(x: V, n: int, h: int, w: int, cin: int, wt: torch.Tensor, cout: int, 
         d.precision = 1
         d.Wt_bf16 = wt16.data_ptr()
     if wt_planes is not None:
-        if (wt_planes.dim() != 2 or wt_planes.shape[0] != 3 or wt_planes.shape[1] != cout * k * k * cin
+        if (wt_planes.dim() != 2 or wt_planes.shape[0] not in (2, 3) or wt_planes.shape[1] != cout * k * k * cin
                 or wt_planes.dtype != torch.int16 or not wt_planes.is_contiguous() or not wt_planes.is_cuda):
-            raise ValueError("conv f32x3 weight planes must be a contiguous int16 CUDA tensor [3, Cout*K]")
-        d.precision = 2
+            raise ValueError("conv split weight planes must be a contiguous int16 CUDA tensor [2 or 3, Cout*K]")
+        d.precision = PREC_BY_PLANES[wt_planes.shape[0]]
         d.Wt_bf16 = wt_planes.data_ptr()
         d.wt_plane_stride = wt_planes.shape[1]
     if ln is not None:
@@ -177,8 +181,8 @@ def conv2d(x: V, n: int, h: int, w: int, cin: int, wt: torch.Tensor, cout: int, 
         d.splitk_counters = counters.data_ptr()
         d.splitk_counters_len = counters.numel()
     # compulsory bytes: activations at their storage width (fp32 or bf16 rows), weights in the operand form
-    # the GEMM streams (fp32, one bf16 plane, or the three split planes)
-    wbytes = 2 if wt16 is not None else 6 if wt_planes is not None else 4
+    # the GEMM streams (fp32, one bf16 plane, or the two / three split planes)
+    wbytes = 2 if wt16 is not None else 2 * wt_planes.shape[0] if wt_planes is not None else 4
     nbytes = (x.t.element_size() * n * h * w * cin + 4 * n * h * w * cin * (a2 is not None)
               + wbytes * cout * k * k * cin + m * cout * (out.t.element_size()
               + (res1.t.element_size() if res1 is not None else 0) + (res2.t.element_size() if res2 is not None else 0)))
@@ -190,13 +194,13 @@ def conv2d(x: V, n: int, h: int, w: int, cin: int, wt: torch.Tensor, cout: int, 
             raise ValueError("conv: Winograd needs a 3x3 stride-1 pad-1 conv without A2 / LayerNorm")
         if wm not in (2, 4):
             raise ValueError("conv: Winograd tile must be 2 or 4")
-        if (planes.dim() != 2 or planes.shape[0] not in (1, 3) or planes.shape[1] != nc * cout * cin
+        if (planes.dim() != 2 or planes.shape[0] not in (1, 2, 3) or planes.shape[1] != nc * cout * cin
                 or planes.dtype != torch.int16 or not planes.is_contiguous() or not planes.is_cuda):
-            raise ValueError(f"conv: Winograd weight planes must be int16 [1 or 3, {nc}*Cout*Cin]")
+            raise ValueError(f"conv: Winograd weight planes must be int16 [1, 2 or 3, {nc}*Cout*Cin]")
         tiles = n * ((h + wm - 1) // wm) * ((w + wm - 1) // wm)
         if work.dtype != torch.float32 or not work.is_cuda or work.numel() < wino_work_elems(wm, tiles, cin, cout):
             raise ValueError("conv: Winograd workspace too small")
-        d.precision = 2 if planes.shape[0] == 3 else 1
+        d.precision = PREC_BY_PLANES[planes.shape[0]]
         d.Wt_bf16 = None
         # three launches (sp_winograd_f23_input / _gemm / _output) so the launch hook times the component
         # GEMM, a batched 1x1 GEMM of 16·T rows in the conv's operand mode, apart from the transforms
@@ -206,12 +210,12 @@ def conv2d(x: V, n: int, h: int, w: int, cin: int, wt: torch.Tensor, cout: int, 
         _launch("wino_tf", f + "_input", (C.byref(d), wp, wn, s), 0, 4 * (n * h * w * cin + v_el), (m, cin, "in"))
         _launch("conv", f + "_gemm", (C.byref(d), planes.data_ptr(), planes.shape[1], wp, wn, s),
                 2 * nc * tiles * cout * cin, 4 * (v_el + m_el) + 2 * planes.numel(),
-                (nc * tiles, cout, cin, 1, 1, "x3" if planes.shape[0] == 3 else "bf16", "wino", m))
+                (nc * tiles, cout, cin, 1, 1, PREC_TAG[d.precision], "wino", m))
         _launch("wino_tf", f + "_output", (C.byref(d), wp, wn, s), 0,
                 4 * (m_el + m * cout * (1 + (res1 is not None) + (res2 is not None))), (m, cout, "out"))
         return ho, wo
     _launch("conv", "sp_conv2d", (C.byref(d), stream()), 2 * m * cout * k * k * cin, nbytes,
-            (m, cout, k * k * cin, k, stride, ("f32", "bf16", "x3")[d.precision] if ln is None else "f32+ln")
+            (m, cout, k * k * cin, k, stride, PREC_TAG[d.precision] if ln is None else "f32+ln")
             + (("rows",) if x.is_bf16 else ())  # "rows": A staged from bf16 rows (tools/tune_conv.py)
             + ("epi:" + ("res" if res1 is not None else "bn" if scale is not None or shift is not None else "none"),))
     return ho, wo
@@ -253,6 +257,15 @@ def split_bf16x3_host(w) -> np.ndarray:
     return np.stack([hi, mid, lo]).view(np.int16)
 
 
+def split_bf16x2_host(w) -> np.ndarray:
+    """fp32 weights (host) → int16 [2, numel] bf16 bit planes hi = RNE(w), lo = RNE(w - hi) (the difference is
+    exact in fp32), so |w - hi - lo| <= 2^-16 |w|: the operand format of SP_PREC_F32X2, the TF32-class tier."""
+    w = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
+    hi = bf16_bits(w)
+    lo = bf16_bits(w - _bf16_float(hi))
+    return np.stack([hi, lo]).view(np.int16)
+
+
 # Winograd F(m×m, 3×3) transform matrices (winograd.hip): F(2×2) on the points (0, 1, -1, ∞); F(4×4) on
 # (0, -1, 1, ½, -2, ∞), chosen for fp32 error. Bᵀ and Aᵀ are what the kernels apply (dyadic, exact in fp32);
 # G is applied here in fp64.
@@ -282,6 +295,11 @@ def winograd_weights_host(wk, m: int = 2) -> np.ndarray:
 def split_bf16x3(w: torch.Tensor) -> torch.Tensor:
     """split_bf16x3_host of a (device) fp32 tensor, uploaded to the tensor's device (tests / tools)."""
     return torch.from_numpy(split_bf16x3_host(w.detach().cpu().numpy())).to(w.device)
+
+
+def split_bf16x2(w: torch.Tensor) -> torch.Tensor:
+    """split_bf16x2_host of a (device) fp32 tensor, uploaded to the tensor's device (tests / tools)."""
+    return torch.from_numpy(split_bf16x2_host(w.detach().cpu().numpy())).to(w.device)
 
 
 def force_conv_config(cfg=None):

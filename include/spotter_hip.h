@@ -294,14 +294,19 @@ int sp_avgpool2x2_ceil_bf16(const uint16_t* x, uint16_t* y, int64_t ldy, int n, 
 /* F.interpolate(scale_factor=2, mode="nearest") into a channel slice (M2:1192). */
 int sp_upsample2x_nearest(const float* x, int64_t ldx, float* y, int64_t ldy, int n, int h,
                           int w, int c, void* stream);
-/* nn.LayerNorm over the last dim (d <= 1024). */
+/* nn.LayerNorm over the last dim (0 < d <= 1024); rows ldx / ldy >= d floats apart (refused otherwise). d % 4 == 0
+ * with ldx, ldy % 4 == 0 and x, y, gamma, beta 16-byte aligned takes the float4 kernels, anything else the scalar
+ * one. */
 int sp_layernorm(const float* x, int64_t ldx, const float* gamma, const float* beta, float* y,
                  int64_t ldy, int rows, int d, float eps, void* stream);
 /* ABI v15. sp_layernorm at d = 256 with the output rounded RNE to bf16 rows: the bf16 variant's encoder head,
- * whose score projection rounds its operand to bf16 anyway (M2:1587-1593). */
+ * whose score projection rounds its operand to bf16 anyway (M2:1587-1593). ldx, ldy % 4 == 0 and >= d; x, gamma,
+ * beta 16-byte and y 8-byte aligned. */
 int sp_layernorm_bf16(const float* x, int64_t ldx, const float* gamma, const float* beta, uint16_t* y, int64_t ldy,
                       int rows, int d, float eps, void* stream);
-/* softmax(Q Kᵀ · scale) V per (batch, head); Q/K/V rows [batch*n, ld], head h at col h*dh. */
+/* softmax(Q Kᵀ · scale) V per (batch, head); Q/K/V rows [batch*n, ld], head h at col h*dh. dh in {32, 48, 64};
+ * every ld % 4 == 0 and >= heads*dh; q, k, v, o 16-byte aligned (float4 loads and stores). Anything else is
+ * refused (-1) before a launch. */
 int sp_attention(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
                  int64_t ldv, float* o, int64_t ldo, int batch, int n, int heads, int dh,
                  float scale, void* stream);

@@ -288,7 +288,13 @@ template <bool BF>
 int attention(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, float* o,
               int64_t ldo, int batch, int n, int heads, int dh, float scale, void* stream) {
   SP_ARG_CHECK(q && k && v && o && batch > 0 && n > 0 && heads > 0, "sp_attention: bad args");
-  SP_ARG_CHECK(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0, "sp_attention: ld % 4");
+  SP_ARG_CHECK(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0, "sp_attention: ld %% 4");
+  // the kernels read and write float4: every row start (base + row·ld + head·dh, all multiples of 4 floats)
+  // is 16-byte aligned exactly when the base is
+  SP_ARG_CHECK((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15) == 0,
+               "sp_attention: q / k / v / o must be 16-byte aligned");
+  const int64_t D = (int64_t)heads * dh;  // a row holds every head's channels (an unsupported dh: refused below)
+  SP_ARG_CHECK(ldq >= D && ldk >= D && ldv >= D && ldo >= D, "sp_attention: ld < heads * dh (%lld)", (long long)D);
   hipStream_t s = as_stream(stream);
   switch (dh) {
     case 32: return launch<32, BF>(q, ldq, k, ldk, v, ldv, o, ldo, batch, n, heads, scale, s);

@@ -526,6 +526,7 @@ extern "C" int sp_upsample2x_nearest(const float* x, int64_t ldx, float* y, int6
 extern "C" int sp_layernorm(const float* x, int64_t ldx, const float* gamma, const float* beta, float* y,
                             int64_t ldy, int rows, int d, float eps, void* stream) {
   SP_ARG_CHECK(x && gamma && beta && y && rows > 0 && d > 0 && d <= 1024, "sp_layernorm: bad args");
+  SP_ARG_CHECK(ldx >= d && ldy >= d, "sp_layernorm: ldx / ldy < d (rows would overlap)");
   const bool vec = d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 &&
                   (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0;
   if (vec && d == 256)
@@ -539,9 +540,10 @@ extern "C" int sp_layernorm(const float* x, int64_t ldx, const float* gamma, con
 
 extern "C" int sp_layernorm_bf16(const float* x, int64_t ldx, const float* gamma, const float* beta, uint16_t* y,
                                  int64_t ldy, int rows, int d, float eps, void* stream) {
-  SP_ARG_CHECK(x && gamma && beta && y && rows > 0 && d == 256 && ldx % 4 == 0 && ldy % 4 == 0 &&
-                   (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0 && ((uintptr_t)y & 7) == 0,
-               "sp_layernorm_bf16: d = 256, ldx / ldy %% 4, 16-byte aligned fp32 rows, 8-byte aligned bf16 rows");
+  SP_ARG_CHECK(x && gamma && beta && y && rows > 0 && d == 256 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= d &&
+                   ldy >= d && (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0 &&
+                   ((uintptr_t)y & 7) == 0,
+               "sp_layernorm_bf16: d = 256, ld %% 4 and >= d, 16-byte aligned fp32 rows, 8-byte aligned bf16 rows");
   hipLaunchKernelGGL(layernorm256_kernel, dim3((rows + 15) / 16), dim3(256), 0, as_stream(stream), x, ldx, gamma,
                      beta, nullptr, y, ldy, rows, eps);
   return check_launch("sp_layernorm_bf16");

@@ -945,7 +945,7 @@ def test_attention(dev, n, heads, dh):
     B = 2
     D = heads * dh
     qkv = rng.standard_normal((B * n, 3 * D)).astype(np.float32)
-    out = torch.empty(B * n * D, device=dev)
+    out = torch.full((B * n * D,), float("nan"), device=dev)
     t = T(qkv.reshape(-1), dev)
     sc = dh ** -0.5
     ops.attention(V(t, 0, 3 * D), V(t, D, 3 * D), V(t, 2 * D, 3 * D), V(out, 0, D), B, n, heads, dh, sc)
@@ -972,8 +972,8 @@ def test_attention_bf16(dev, n, heads, dh):
     B, D = 2, heads * dh
     qkv = rng.standard_normal((B * n, 3 * D)).astype(np.float32)
     t = T(qkv.reshape(-1), dev)
-    out = torch.empty(B * n * D, device=dev)
-    out32 = torch.empty(B * n * D, device=dev)
+    out = torch.full((B * n * D,), float("nan"), device=dev)
+    out32 = torch.full((B * n * D,), float("nan"), device=dev)
     sc = dh ** -0.5
     args = (V(t, 0, 3 * D), V(t, D, 3 * D), V(t, 2 * D, 3 * D))
     ops.attention(*args, V(out, 0, D), B, n, heads, dh, sc, bf16=True)

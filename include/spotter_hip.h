@@ -41,8 +41,9 @@ enum sp_act { SP_ACT_NONE = 0, SP_ACT_RELU = 1, SP_ACT_SILU = 2, SP_ACT_GELU = 3
  *  SP_PREC_F32X3 fp32 operands as 3-way bf16 splits x = hi + mid + lo (24 significand bits,
  *                exact for normal fp32), products hi·hi + hi·mid + mid·hi + hi·lo + lo·hi +
  *                mid·mid on bf16 MFMA with fp32 accumulate; the dropped terms sum to <= 2^-24
- *                of |a·b| (one fp32 rounding), so the result is fp32-accurate (checked against
- *                fp64 next to the fp32 MFMA path in tests/test_gpu_kernels.py).
+ *                of |a·b| (one fp32 rounding), so the result is fp32-accurate (every instance checked
+ *                against fp64: bit-exact on the six kept products, and inside a derived per-element
+ *                bound, in tests/test_gpu_conv_plans.py).
  *                Weights from Wt_bf16 as three planes [3][Cout][K] (plane stride
  *                wt_plane_stride); activations are split while staging;
  *  SP_PREC_F32X2 (ABI v19) the TF32-class tier: fp32 operands as 2-way bf16 splits x = hi + lo + rho with

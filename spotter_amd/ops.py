@@ -77,17 +77,16 @@ def view(t: torch.Tensor, ld: int | None = None, off: int = 0) -> V:
     return V(t, off, ld if ld is not None else t.shape[-1])
 
 
-def conv2d(x: V, n: int, h: int, w: int, cin: int, wt: torch.Tensor, cout: int, k: int, stride: int,
-           pad: int, out: V, *, scale=None, shift=None, act=None, res1: V | None = None,
-           res2: V | None = None, a2: V | None = None, row_scale: torch.Tensor | None = None,
-           rows_per_group: int = 0, group_stride: int = 0, workspace: torch.Tensor | None = None,
-           wt16: torch.Tensor | None = None, wt_planes: torch.Tensor | None = None, ln=None, wino=None,
-           counters: torch.Tensor | None = None):
-    """ln = (gamma, beta, eps): LayerNorm over each output row fused into the epilogue (fp32 weights).
-    wino = (planes, work[, m]): run this 3×3 stride-1 conv as Winograd F(m×m, 3×3), m = 2 (default) or 4
-    (sp_winograd_f23_* / _f43_*), on the transformed weight planes (int16 [3 or 1, (m+2)²·Cout·Cin],
-    winograd_weights_host + split; 2 planes: the 2-way split) with the fp32 scratch `work`; the bf16 / split
-    operand mode follows the plane count.
+def conv_desc(x: V, n: int, h: int, w: int, cin: int, wt: torch.Tensor, cout: int, k: int, stride: int,
+              pad: int, out: V, *, scale=None, shift=None, act=None, res1: V | None = None,
+              res2: V | None = None, a2: V | None = None, row_scale: torch.Tensor | None = None,
+              rows_per_group: int = 0, group_stride: int = 0, workspace: torch.Tensor | None = None,
+              wt16: torch.Tensor | None = None, wt_planes: torch.Tensor | None = None, ln=None,
+              counters: torch.Tensor | None = None):
+    """The checked sp_conv_desc of one conv2d call (every operand span verified against its tensor) and the
+    launch hook's accounting of it: (desc, (flops, nbytes, shape)). conv_plan(desc) names the instance
+    sp_conv2d would run for it, conv_launch(desc, hook_args) launches it; conv2d is the two together.
+    ln = (gamma, beta, eps): LayerNorm over each output row fused into the epilogue (fp32 weights).
     counters (int32, zeroed once by the caller, one per stream): split-K launches combine their partial sums
     inside the GEMM launch (sp_conv_desc.splitk_counters, ABI v13) instead of a second reduce launch.
     wt16 (int16 bit patterns of bf16 weights, same [Cout][K] layout) selects the bf16 MFMA path;
@@ -186,6 +185,34 @@ def conv2d(x: V, n: int, h: int, w: int, cin: int, wt: torch.Tensor, cout: int, 
     nbytes = (x.t.element_size() * n * h * w * cin + 4 * n * h * w * cin * (a2 is not None)
               + wbytes * cout * k * k * cin + m * cout * (out.t.element_size()
               + (res1.t.element_size() if res1 is not None else 0) + (res2.t.element_size() if res2 is not None else 0)))
+    shape = ((m, cout, k * k * cin, k, stride, PREC_TAG[d.precision] if ln is None else "f32+ln")
+             + (("rows",) if x.is_bf16 else ())  # "rows": A staged from bf16 rows (tools/tune_conv.py)
+             + ("epi:" + ("res" if res1 is not None else "bn" if scale is not None or shift is not None else "none"),))
+    return d, (2 * m * cout * k * k * cin, nbytes, shape)
+
+
+def conv_launch(d, hook_args):
+    """Launch sp_conv2d on a conv_desc result (the operands' tensors must still be alive)."""
+    flops, nbytes, shape = hook_args
+    _launch("conv", "sp_conv2d", (C.byref(d), stream()), flops, nbytes, shape)
+
+
+def conv2d(x: V, n: int, h: int, w: int, cin: int, wt: torch.Tensor, cout: int, k: int, stride: int,
+           pad: int, out: V, *, scale=None, shift=None, act=None, res1: V | None = None,
+           res2: V | None = None, a2: V | None = None, row_scale: torch.Tensor | None = None,
+           rows_per_group: int = 0, group_stride: int = 0, workspace: torch.Tensor | None = None,
+           wt16: torch.Tensor | None = None, wt_planes: torch.Tensor | None = None, ln=None, wino=None,
+           counters: torch.Tensor | None = None):
+    """sp_conv2d on conv_desc's descriptor (see there for the operands), or, with
+    wino = (planes, work[, m]): this 3×3 stride-1 conv as Winograd F(m×m, 3×3), m = 2 (default) or 4
+    (sp_winograd_f23_* / _f43_*), on the transformed weight planes (int16 [3 or 1, (m+2)²·Cout·Cin],
+    winograd_weights_host + split; 2 planes: the 2-way split) with the fp32 scratch `work`; the bf16 / split
+    operand mode follows the plane count."""
+    d, hook_args = conv_desc(x, n, h, w, cin, wt, cout, k, stride, pad, out, scale=scale, shift=shift, act=act,
+                             res1=res1, res2=res2, a2=a2, row_scale=row_scale, rows_per_group=rows_per_group,
+                             group_stride=group_stride, workspace=workspace, wt16=wt16, wt_planes=wt_planes, ln=ln,
+                             counters=counters)
+    ho, wo, m = d.Ho, d.Wo, d.N * d.Ho * d.Wo
     if wino is not None:
         planes, work = wino[0], wino[1]
         wm = wino[2] if len(wino) > 2 else 2
@@ -214,10 +241,7 @@ def conv2d(x: V, n: int, h: int, w: int, cin: int, wt: torch.Tensor, cout: int, 
         _launch("wino_tf", f + "_output", (C.byref(d), wp, wn, s), 0,
                 4 * (m_el + m * cout * (1 + (res1 is not None) + (res2 is not None))), (m, cout, "out"))
         return ho, wo
-    _launch("conv", "sp_conv2d", (C.byref(d), stream()), 2 * m * cout * k * k * cin, nbytes,
-            (m, cout, k * k * cin, k, stride, PREC_TAG[d.precision] if ln is None else "f32+ln")
-            + (("rows",) if x.is_bf16 else ())  # "rows": A staged from bf16 rows (tools/tune_conv.py)
-            + ("epi:" + ("res" if res1 is not None else "bn" if scale is not None or shift is not None else "none"),))
+    conv_launch(d, hook_args)
     return ho, wo
 
 

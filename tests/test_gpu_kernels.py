@@ -96,7 +96,7 @@ def test_conv2d_matches_oracle(dev, case, workspace=None):
     r1 = rng.standard_normal((m, cout)).astype(np.float32)
     r2 = rng.standard_normal((m, cout)).astype(np.float32)
     ref = conv_ref(x, wt, st, pad, sc, sh, act, r1, r2)
-    out = torch.empty(m * cout, device=dev)
+    out = torch.full((m * cout,), float("nan"), device=dev)  # an element no kernel stores fails the comparison
     wk = T(wt.transpose(0, 2, 3, 1).reshape(cout, -1), dev)
     ops.conv2d(view(T(x.reshape(-1), dev), cin), n, h, w, cin, wk, cout, k, st, pad, view(out, cout),
                scale=T(sc, dev), shift=T(sh, dev), act=act, res1=view(T(r1.reshape(-1), dev), cout),
@@ -242,7 +242,7 @@ def test_conv2d_bf16_matches_bf16_rounded_reference(dev, case, cfg, monkeypatch)
     m = n * ho * wo
     r1 = rng.standard_normal((m, cout)).astype(np.float32)
     ref = conv_ref(_bf16(x), _bf16(wt), st, pad, sc, sh, act, r1, None)
-    out = torch.empty(m * cout, device=dev)
+    out = torch.full((m * cout,), float("nan"), device=dev)
     wk = wt.transpose(0, 2, 3, 1).reshape(cout, -1)
     w16 = torch.from_numpy(bf16_bits(wk).view(np.int16)).to(dev)
     ws = torch.empty(4 << 20, device=dev)
@@ -288,7 +288,7 @@ def test_conv2d_f32x3_is_fp32_accurate(dev, case, cfg, monkeypatch):
     for mode in ("fp32", "f32x3"):
         if mode == "f32x3" and cfg:
             ops.force_conv_config(cfg)
-        out = torch.empty(m * cout, device=dev)
+        out = torch.full((m * cout,), float("nan"), device=dev)
         ops.conv2d(xd, n, h, w, cin, wk, cout, k, st, pad, view(out, cout), workspace=ws,
                    wt_planes=ops.split_bf16x3(wk) if mode == "f32x3" else None)
         outs[mode] = out.cpu().numpy().reshape(m, cout).astype(np.float64)
@@ -332,7 +332,7 @@ def test_winograd_is_fp32_accurate(dev, case, cfg, wm):
     wk_host = wt.transpose(0, 2, 3, 1)
     wk = T(wk_host.reshape(cout, -1), dev)
     xd = view(T(x.reshape(-1), dev), cin)
-    out32 = torch.empty(m * cout, device=dev)
+    out32 = torch.full((m * cout,), float("nan"), device=dev)
     ops.conv2d(xd, n, h, w, cin, wk, cout, 3, 1, 1, view(out32, cout))
     planes = T(ops.split_bf16x3_host(ops.winograd_weights_host(wk_host, wm)), dev)
     tiles = n * ((h + wm - 1) // wm) * ((w + wm - 1) // wm)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SP_ABI_VERSION 19
+#define SP_ABI_VERSION 20
 
 enum sp_act { SP_ACT_NONE = 0, SP_ACT_RELU = 1, SP_ACT_SILU = 2, SP_ACT_GELU = 3 };
 /* GEMM operand precision:
@@ -219,7 +219,10 @@ int sp_conv_plan(const sp_conv_desc* d, sp_conv_plan_info* out);
  * operands), computed as input transform V = B^T d B per 2x2 output tile → 16 batched GEMMs
  * V_ab · U_ab on the split (SP_PREC_F32X3 / SP_PREC_F32X2) or bf16 (SP_PREC_BF16) MFMA kernels → output transform
  * Y = A^T M A + the fused epilogue. 2.25x fewer GEMM multiply-adds than the implicit GEMM; fp32 error
- * on par with the direct fp32 conv. wt_wino: the transformed weights U = G g G^T (computed in fp64 on
+ * on par with the direct fp32 conv. Each stage is tested on its own against fp64 (tests/test_gpu_winograd.py on
+ * tests/wino_refs.py: both transforms bit for bit on integers, the component GEMM bit for bit on its kept-product
+ * model, the whole path bit for bit on impulses; on N(0,1) / offset / post-relu maps the worst error over the
+ * derived bound is 0.49 for either transform, 0.12 / 0.07 / 0.30 for the whole path in x3 / x2 / bf16). wt_wino: the transformed weights U = G g G^T (computed in fp64 on
  * the host, rounded to fp32) as bf16 planes [planes][16][Cout][Cin] (component ab = 4a + b), planes
  * wino_plane_stride elements apart (3 planes for SP_PREC_F32X3, 2 for SP_PREC_F32X2, 1 for SP_PREC_BF16); d->Wt /
  * d->Wt_bf16 are not read. work: fp32 scratch of >= 16 * T * (Cin + Cout) elements,
@@ -239,11 +242,30 @@ int sp_winograd_f23_output(const sp_conv_desc* d, const float* work, int64_t wor
  * components (component ab = 6a + b), interpolation points (0, -1, 1, 1/2, -2, inf); wt_wino
  * [planes][36][Cout][Cin] (U = G g G^T in fp64 on the host), work >= 36 * T * (Cin + Cout) elements.
  * 1/4 of the direct conv's multiply-adds; fp32 error 3-5x the direct conv's, under 1e-5 of the output
- * scale (tests/test_gpu_kernels.py::test_winograd_is_fp32_accurate). */
+ * scale (tests/test_gpu_kernels.py::test_winograd_is_fp32_accurate). Stage by stage against fp64 in
+ * tests/test_gpu_winograd.py (test_input_transform[4], test_output_transform[4], test_component_gemm,
+ * test_whole_path, test_grid_stride_loop[in4 / out4]): exact families bit-identical; worst error over the
+ * derived bound 0.45 (input), 0.50 (output), 0.21 / 0.04 / 0.22 (whole path, x3 / x2 / bf16). */
 int sp_winograd_f43_input(const sp_conv_desc* d, float* work, int64_t work_elems, void* stream);
 int sp_winograd_f43_gemm(const sp_conv_desc* d, const uint16_t* wt_wino, int64_t wino_plane_stride, float* work,
                          int64_t work_elems, void* stream);
 int sp_winograd_f43_output(const sp_conv_desc* d, const float* work, int64_t work_elems, void* stream);
+/* What the Winograd stages would run for a descriptor (ABI v20), under the calling thread's sp_set_conv_config:
+ * the stages' argument checks (all but the work / wt_wino pointers, which it does not take) and the component
+ * GEMM's tile rule, without a launch or a device call. wm = 2 or 4 (F(2x2) / F(4x4)); wino_plane_stride and
+ * work_elems as the stages take them. The stages launch from the same function, so plan and launch cannot
+ * disagree. Returns 0, or < 0 with the sp_last_error text the stages would give.
+ * The stages refuse (each with its own message) lda < Cin, ldc < Cout, ldr1 / ldr2 < Cout for a given residual,
+ * and any of A_bf16 / C_bf16 / res1_bf16 / res2_bf16: they read and write fp32 rows only. */
+typedef struct {
+  sp_conv_plan_info gemm; /* the batched component GEMM's instance (family SP_CONV_GLDS) */
+  int32_t components;     /* 16 or 36: GEMMs in the batch */
+  int32_t in_vw;          /* channels per thread of the input transform: 4 for F(2x2); 1 or 2 for F(4x4) */
+  int32_t out_vw;         /* ... of the output transform */
+  int64_t tiles;          /* T = N * ceil(H/wm) * ceil(W/wm): rows of each component GEMM */
+} sp_winograd_plan_info;
+int sp_winograd_plan(const sp_conv_desc* d, int wm, int64_t wino_plane_stride, int64_t work_elems,
+                     sp_winograd_plan_info* out);
 
 /* NCHW → NHWC (pixel_values layout of the processor contract → conv layout). */
 int sp_nchw_to_nhwc(const float* x, float* y, int n, int c, int h, int w, void* stream);

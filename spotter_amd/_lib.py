@@ -13,7 +13,7 @@ import threading
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPOTTER_HIP_LIB", os.path.join(HERE, "libspotter_hip.so"))
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -51,6 +51,10 @@ class SpConvDesc(C.Structure):
 class SpConvPlanInfo(C.Structure):
     _fields_ = [(f, i32) for f in ("family", "tile", "planes", "generic", "a_bf16", "fast_1x1", "epilogue", "splits",
                                    "counters")]
+
+
+class SpWinogradPlanInfo(C.Structure):
+    _fields_ = [("gemm", SpConvPlanInfo), ("components", i32), ("in_vw", i32), ("out_vw", i32), ("tiles", i64)]
 
 
 class SpMsdaDesc(C.Structure):
@@ -124,6 +128,7 @@ _SIGS = {
     "sp_set_splitk_config": (i32, [i32, i32, i32]),
     "sp_set_tuning": (i32, [i32, i32]),
     "sp_conv_plan": (i32, [C.POINTER(SpConvDesc), C.POINTER(SpConvPlanInfo)]),
+    "sp_winograd_plan": (i32, [C.POINTER(SpConvDesc), i32, i64, i64, C.POINTER(SpWinogradPlanInfo)]),
     "sp_conv3x3_winograd": (i32, [C.POINTER(SpConvDesc), vp, i64, vp, i64, vp]),
     "sp_winograd_f23_input": (i32, [C.POINTER(SpConvDesc), vp, i64, vp]),
     "sp_winograd_f23_gemm": (i32, [C.POINTER(SpConvDesc), vp, i64, vp, i64, vp]),

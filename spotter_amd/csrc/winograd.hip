@@ -9,7 +9,9 @@
 // The GEMMs carry 16/36 of the direct conv's multiply-adds (2.25× fewer) and run on the batched
 // LDS-DMA kernels of conv_glds.hip in any operand mode (x3 split: fp32-accurate; bf16). In fp32 the
 // transforms add two roundings on each side; the error measured against fp64 matches the direct fp32
-// conv's (the GEMM's K is 9× shorter) — tests/test_gpu_kernels.py::test_winograd_*.
+// conv's (the GEMM's K is 9× shorter) — tests/test_gpu_kernels.py::test_winograd_*; each stage against an fp64
+// reference of its own (bit for bit on integer / impulse operands, per element inside a derived bound otherwise):
+// tests/test_gpu_winograd.py on tests/wino_refs.py, DESIGN 5.14.
 //
 // Layout: V [16][T][Cin] and M [16][T][Cout] fp32 in the caller's workspace, T = N·⌈H/2⌉·⌈W/2⌉ tiles
 // (b, ty, tx) row-major; component ab = 4a + b. The transform kernels are HBM-bound streams with
@@ -323,17 +325,22 @@ bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 namespace sp {
 namespace {
 
-// Validation shared by the Winograd entry points (output tiles MT × MT: 2 for F(2×2,3×3), 4 for
-// F(4×4,3×3); NC = (MT + 2)² components); fills th, tw, T. wt_wino may be null (the transform stages
-// do not read it).
+// Validation shared by the Winograd entry points and sp_winograd_plan (output tiles MT × MT: 2 for
+// F(2×2,3×3), 4 for F(4×4,3×3); NC = (MT + 2)² components); fills th, tw, T. `ptrs`: the call launches, so
+// work (and, with need_wt, wt_wino) must be given and aligned; the plan query passes neither. need_wt: the
+// component GEMM's weight-plane checks (the transform stages do not read the planes).
 // Floats of the workspace that V occupies (M follows): NC·T·Cin fp32.
 int64_t wino_v_floats(int nc, int64_t T, int cin) { return (int64_t)nc * T * cin; }
 
 template <int MT>
 int wino_check(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino, int64_t wino_plane_stride,
-               const float* work, int64_t work_elems, bool need_wt, int* th, int* tw, int64_t* T) {
+               const float* work, int64_t work_elems, bool need_wt, bool ptrs, int* th, int* tw, int64_t* T) {
   constexpr int NC = (MT + 2) * (MT + 2);
-  SP_ARG_CHECK(d != nullptr && work != nullptr && (!need_wt || wt_wino != nullptr), "%s: null argument", what);
+  SP_ARG_CHECK(d != nullptr && (!ptrs || (work != nullptr && (!need_wt || wt_wino != nullptr))),
+               "%s: null argument", what);
+  // fp32 rows only: the transforms read A / res1 / res2 and write C as fp32 (a bf16 field would be ignored)
+  SP_ARG_CHECK(!d->A_bf16 && !d->C_bf16 && !d->res1_bf16 && !d->res2_bf16,
+               "%s: bf16 rows (A_bf16 / C_bf16 / res1_bf16 / res2_bf16) are not supported", what);
   SP_ARG_CHECK(d->A && d->C, "%s: null A/C", what);
   SP_ARG_CHECK(d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->Ho == d->H && d->Wo == d->W,
                "%s: needs a 3x3 stride-1 pad-1 conv (KH=%d KW=%d stride=%d pad=%d)", what, d->KH, d->KW, d->stride,
@@ -341,6 +348,10 @@ int wino_check(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino,
   SP_ARG_CHECK(d->N > 0 && d->H > 0 && d->W > 0, "%s: bad shape", what);
   SP_ARG_CHECK(d->Cin % 32 == 0 && d->Cout % 4 == 0 && d->Cout > 0,
                "%s: needs Cin %% 32 == 0, Cout %% 4 == 0 (Cin=%d Cout=%d)", what, d->Cin, d->Cout);
+  SP_ARG_CHECK(d->lda >= d->Cin, "%s: lda %lld < Cin %d", what, (long long)d->lda, d->Cin);
+  SP_ARG_CHECK(d->ldc >= d->Cout, "%s: ldc %lld < Cout %d", what, (long long)d->ldc, d->Cout);
+  SP_ARG_CHECK(!d->res1 || d->ldr1 >= d->Cout, "%s: ldr1 %lld < Cout %d", what, (long long)d->ldr1, d->Cout);
+  SP_ARG_CHECK(!d->res2 || d->ldr2 >= d->Cout, "%s: ldr2 %lld < Cout %d", what, (long long)d->ldr2, d->Cout);
   SP_ARG_CHECK(d->precision == SP_PREC_F32X3 || d->precision == SP_PREC_F32X2 || d->precision == SP_PREC_BF16,
                "%s: precision %d (split or bf16 operands)", what, d->precision);
   SP_ARG_CHECK(!d->A2 && !d->row_scale && d->out_rows_per_group == 0 && !d->ln_gamma,
@@ -364,39 +375,33 @@ int wino_check(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino,
   return 0;
 }
 
-template <int MT>
-int wino_input(const char* what, const sp_conv_desc* d, float* work, int64_t work_elems, void* stream) {
-  constexpr int NC = (MT + 2) * (MT + 2);
+// Everything a Winograd stage launches from, decided in one place (sp_winograd_plan reports it; wino_input /
+// wino_gemm / wino_output launch from it, so the plan and the launch cannot disagree): the tile grid, the
+// channels per thread of the two transforms and, with `gemm`, the component GEMM's arguments and instance.
+struct WinoPlan {
   int th, tw;
   int64_t T;
-  if (int rc = wino_check<MT>(what, d, nullptr, 0, work, work_elems, false, &th, &tw, &T)) return rc;
-  if constexpr (MT == 2) {
-    const int cin4 = d->Cin / 4;
-    const int64_t pairs = (int64_t)d->N * th * ((tw + 1) / 2);
-    hipLaunchKernelGGL(wino_in_f23_x2_kernel, dim3(stream_grid(pairs * cin4)), dim3(256), 0, as_stream(stream),
-                       d->A, d->lda, d->H, d->W, cin4, th, tw, (int64_t)d->N, work, (int64_t)d->Cin);
-  } else {
-    const int64_t ts = d->Cin, cs = T * d->Cin;
-    if (wino43_in_vw(T * d->Cin) == 1)
-      hipLaunchKernelGGL(wino_in_f43_kernel<1>, dim3(stream_grid(T * d->Cin)), dim3(256), 0, as_stream(stream),
-                         d->A, d->lda, d->H, d->W, d->Cin, th, tw, T, work, ts, cs);
-    else
-      hipLaunchKernelGGL(wino_in_f43_kernel<2>, dim3(stream_grid(T * d->Cin / 2)), dim3(256), 0, as_stream(stream),
-                         d->A, d->lda, d->H, d->W, d->Cin / 2, th, tw, T, work, ts, cs);
-  }
-  return check_launch(what);
-}
+  int in_vw, out_vw;  // channels per thread: 4 for the F(2×2) kernels (float4), 1 or 2 for F(4×4)
+  int planes;
+  ConvArgs g;
+  ConvPlan p;
+};
 
 template <int MT>
-int wino_gemm(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino, int64_t wino_plane_stride,
-              float* work, int64_t work_elems, void* stream) {
+int wino_plan(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino, int64_t wino_plane_stride,
+              float* work, int64_t work_elems, bool gemm, bool ptrs, WinoPlan* w) {
   constexpr int NC = (MT + 2) * (MT + 2);
-  int th, tw;
-  int64_t T;
-  if (int rc = wino_check<MT>(what, d, wt_wino, wino_plane_stride, work, work_elems, true, &th, &tw, &T)) return rc;
-  const int planes = d->precision == SP_PREC_BF16 ? 1 : d->precision == SP_PREC_F32X2 ? 2 : 3;
+  if (int rc = wino_check<MT>(what, d, wt_wino, wino_plane_stride, work, work_elems, gemm, ptrs, &w->th, &w->tw,
+                              &w->T))
+    return rc;
+  const int64_t T = w->T;
+  w->in_vw = MT == 2 ? 4 : wino43_in_vw(T * d->Cin);
+  w->out_vw = MT == 2 ? 4 : wino43_out_vw();
+  w->planes = d->precision == SP_PREC_BF16 ? 1 : d->precision == SP_PREC_F32X2 ? 2 : 3;
+  if (!gemm) return 0;
+  const int planes = w->planes;
   // the NC component GEMMs as one batched launch: M = T tiles, K = Cin, no epilogue
-  ConvArgs g;
+  ConvArgs& g = w->g;
   memset(&g.d, 0, sizeof(g.d));
   const int64_t voff = wino_v_floats(NC, T, d->Cin);
   g.d.A = work;
@@ -411,7 +416,7 @@ int wino_gemm(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino, 
   g.d.Ho = 1;
   g.d.Wo = (int32_t)T;
   g.d.Cout = d->Cout;
-  g.d.C = work + voff;
+  g.d.C = work ? work + voff : nullptr;
   g.d.ldc = d->Cout;
   g.d.precision = d->precision;
   g.d.Wt_bf16 = wt_wino;
@@ -451,24 +456,54 @@ int wino_gemm(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino, 
     else if (d->Cout <= 256) cfg = 246;
     else cfg = 245;
   }
-  ConvPlan p;
-  if (int rc = plan_glds(g, planes, cfg, what, &p)) return rc;
-  return launch_glds(g, p, as_stream(stream));
+  return plan_glds(g, planes, cfg, what, &w->p);
+}
+
+template <int MT>
+int wino_input(const char* what, const sp_conv_desc* d, float* work, int64_t work_elems, void* stream) {
+  WinoPlan w;
+  if (int rc = wino_plan<MT>(what, d, nullptr, 0, work, work_elems, false, true, &w)) return rc;
+  const int th = w.th, tw = w.tw;
+  const int64_t T = w.T;
+  if constexpr (MT == 2) {
+    const int cin4 = d->Cin / 4;
+    const int64_t pairs = (int64_t)d->N * th * ((tw + 1) / 2);
+    hipLaunchKernelGGL(wino_in_f23_x2_kernel, dim3(stream_grid(pairs * cin4)), dim3(256), 0, as_stream(stream),
+                       d->A, d->lda, d->H, d->W, cin4, th, tw, (int64_t)d->N, work, (int64_t)d->Cin);
+  } else {
+    const int64_t ts = d->Cin, cs = T * d->Cin;
+    if (w.in_vw == 1)
+      hipLaunchKernelGGL(wino_in_f43_kernel<1>, dim3(stream_grid(T * d->Cin)), dim3(256), 0, as_stream(stream),
+                         d->A, d->lda, d->H, d->W, d->Cin, th, tw, T, work, ts, cs);
+    else
+      hipLaunchKernelGGL(wino_in_f43_kernel<2>, dim3(stream_grid(T * d->Cin / 2)), dim3(256), 0, as_stream(stream),
+                         d->A, d->lda, d->H, d->W, d->Cin / 2, th, tw, T, work, ts, cs);
+  }
+  return check_launch(what);
+}
+
+template <int MT>
+int wino_gemm(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino, int64_t wino_plane_stride,
+              float* work, int64_t work_elems, void* stream) {
+  WinoPlan w;
+  if (int rc = wino_plan<MT>(what, d, wt_wino, wino_plane_stride, work, work_elems, true, true, &w)) return rc;
+  return launch_glds(w.g, w.p, as_stream(stream));
 }
 
 template <int MT>
 int wino_output(const char* what, const sp_conv_desc* d, const float* work, int64_t work_elems, void* stream) {
   constexpr int NC = (MT + 2) * (MT + 2);
-  int th, tw;
-  int64_t T;
-  if (int rc = wino_check<MT>(what, d, nullptr, 0, work, work_elems, false, &th, &tw, &T)) return rc;
+  WinoPlan w;
+  if (int rc = wino_plan<MT>(what, d, nullptr, 0, const_cast<float*>(work), work_elems, false, true, &w)) return rc;
+  const int th = w.th, tw = w.tw;
+  const int64_t T = w.T;
   if constexpr (MT == 2) {
     const int cout4 = d->Cout / 4;
     hipLaunchKernelGGL(wino_out_f23_kernel, dim3(stream_grid(T * cout4)), dim3(256), 0, as_stream(stream),
                        work + wino_v_floats(NC, T, d->Cin), T, cout4, th, tw, *d);
   } else {
     const int64_t ts = d->Cout, cs = T * d->Cout;
-    if (wino43_out_vw() == 1)
+    if (w.out_vw == 1)
       hipLaunchKernelGGL(wino_out_f43_kernel<1>, dim3(stream_grid(T * d->Cout)), dim3(256), 0, as_stream(stream),
                          work + wino_v_floats(NC, T, d->Cin), T, d->Cout, th, tw, *d, ts, cs);
     else
@@ -476,6 +511,19 @@ int wino_output(const char* what, const sp_conv_desc* d, const float* work, int6
                          as_stream(stream), work + wino_v_floats(NC, T, d->Cin), T, d->Cout / 2, th, tw, *d, ts, cs);
   }
   return check_launch(what);
+}
+
+template <int MT>
+int wino_plan_info(const sp_conv_desc* d, int64_t wino_plane_stride, int64_t work_elems, sp_winograd_plan_info* out) {
+  WinoPlan w;
+  if (int rc = wino_plan<MT>("sp_winograd_plan", d, nullptr, wino_plane_stride, nullptr, work_elems, true, false, &w))
+    return rc;
+  out->gemm = w.p;
+  out->components = (MT + 2) * (MT + 2);
+  out->in_vw = w.in_vw;
+  out->out_vw = w.out_vw;
+  out->tiles = w.T;
+  return 0;
 }
 
 }  // namespace
@@ -512,4 +560,11 @@ extern "C" int sp_winograd_f43_gemm(const sp_conv_desc* d, const uint16_t* wt_wi
 
 extern "C" int sp_winograd_f43_output(const sp_conv_desc* d, const float* work, int64_t work_elems, void* stream) {
   return sp::wino_output<4>("sp_winograd_f43_output", d, work, work_elems, stream);
+}
+
+extern "C" int sp_winograd_plan(const sp_conv_desc* d, int wm, int64_t wino_plane_stride, int64_t work_elems,
+                                sp_winograd_plan_info* out) {
+  SP_ARG_CHECK(out != nullptr && (wm == 2 || wm == 4), "sp_winograd_plan: null out, or wm %d (2 or 4)", wm);
+  return wm == 2 ? sp::wino_plan_info<2>(d, wino_plane_stride, work_elems, out)
+                 : sp::wino_plan_info<4>(d, wino_plane_stride, work_elems, out);
 }

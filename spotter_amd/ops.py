@@ -212,34 +212,9 @@ def conv2d(x: V, n: int, h: int, w: int, cin: int, wt: torch.Tensor, cout: int, 
                              res1=res1, res2=res2, a2=a2, row_scale=row_scale, rows_per_group=rows_per_group,
                              group_stride=group_stride, workspace=workspace, wt16=wt16, wt_planes=wt_planes, ln=ln,
                              counters=counters)
-    ho, wo, m = d.Ho, d.Wo, d.N * d.Ho * d.Wo
+    ho, wo = d.Ho, d.Wo
     if wino is not None:
-        planes, work = wino[0], wino[1]
-        wm = wino[2] if len(wino) > 2 else 2
-        nc = (wm + 2) ** 2
-        if k != 3 or stride != 1 or pad != 1 or ln is not None or a2 is not None:
-            raise ValueError("conv: Winograd needs a 3x3 stride-1 pad-1 conv without A2 / LayerNorm")
-        if wm not in (2, 4):
-            raise ValueError("conv: Winograd tile must be 2 or 4")
-        if (planes.dim() != 2 or planes.shape[0] not in (1, 2, 3) or planes.shape[1] != nc * cout * cin
-                or planes.dtype != torch.int16 or not planes.is_contiguous() or not planes.is_cuda):
-            raise ValueError(f"conv: Winograd weight planes must be int16 [1, 2 or 3, {nc}*Cout*Cin]")
-        tiles = n * ((h + wm - 1) // wm) * ((w + wm - 1) // wm)
-        if work.dtype != torch.float32 or not work.is_cuda or work.numel() < wino_work_elems(wm, tiles, cin, cout):
-            raise ValueError("conv: Winograd workspace too small")
-        d.precision = PREC_BY_PLANES[planes.shape[0]]
-        d.Wt_bf16 = None
-        # three launches (sp_winograd_f23_input / _gemm / _output) so the launch hook times the component
-        # GEMM, a batched 1x1 GEMM of 16·T rows in the conv's operand mode, apart from the transforms
-        wp, wn, s = work.data_ptr(), work.numel(), stream()
-        v_el, m_el = nc * tiles * cin, nc * tiles * cout
-        f = f"sp_winograd_f{wm}3"
-        _launch("wino_tf", f + "_input", (C.byref(d), wp, wn, s), 0, 4 * (n * h * w * cin + v_el), (m, cin, "in"))
-        _launch("conv", f + "_gemm", (C.byref(d), planes.data_ptr(), planes.shape[1], wp, wn, s),
-                2 * nc * tiles * cout * cin, 4 * (v_el + m_el) + 2 * planes.numel(),
-                (nc * tiles, cout, cin, 1, 1, PREC_TAG[d.precision], "wino", m))
-        _launch("wino_tf", f + "_output", (C.byref(d), wp, wn, s), 0,
-                4 * (m_el + m * cout * (1 + (res1 is not None) + (res2 is not None))), (m, cout, "out"))
+        wino_launch(wino_desc(d, wino))
         return ho, wo
     conv_launch(d, hook_args)
     return ho, wo
@@ -249,6 +224,68 @@ def wino_work_elems(wm: int, tiles: int, cin: int, cout: int) -> int:
     """fp32 workspace of one Winograd F(wm×wm, 3×3) conv (winograd.hip): V then M."""
     nc = (wm + 2) ** 2
     return nc * tiles * (cin + cout)
+
+
+def wino_desc(d, wino):
+    """The checked Winograd form of a conv_desc descriptor: wino = (planes, work[, m]) as conv2d takes it. Sets the
+    descriptor's operand mode from the plane count and returns the three stage launches (input, gemm, output) as
+    _launch argument tuples on that very descriptor: wino_launch(stages) runs them, wino_plan(d, m, ...) names
+    what they would run. The operands' tensors (planes and work included) must stay alive until the launch."""
+    planes, work = wino[0], wino[1]
+    wm = wino[2] if len(wino) > 2 else 2
+    nc = (wm + 2) ** 2
+    n, h, w, cin, cout = d.N, d.H, d.W, d.Cin, d.Cout
+    m = n * d.Ho * d.Wo
+    if d.KH != 3 or d.KW != 3 or d.stride != 1 or d.pad != 1 or d.ln_gamma or d.A2:
+        raise ValueError("conv: Winograd needs a 3x3 stride-1 pad-1 conv without A2 / LayerNorm")
+    if wm not in (2, 4):
+        raise ValueError("conv: Winograd tile must be 2 or 4")
+    if (planes.dim() != 2 or planes.shape[0] not in (1, 2, 3) or planes.shape[1] != nc * cout * cin
+            or planes.dtype != torch.int16 or not planes.is_contiguous() or not planes.is_cuda):
+        raise ValueError(f"conv: Winograd weight planes must be int16 [1, 2 or 3, {nc}*Cout*Cin]")
+    tiles = n * ((h + wm - 1) // wm) * ((w + wm - 1) // wm)
+    if work.dtype != torch.float32 or not work.is_cuda or work.numel() < wino_work_elems(wm, tiles, cin, cout):
+        raise ValueError("conv: Winograd workspace too small")
+    d.precision = PREC_BY_PLANES[planes.shape[0]]
+    d.Wt_bf16 = None
+    # three launches (sp_winograd_f23_input / _gemm / _output) so the launch hook times the component
+    # GEMM, a batched 1x1 GEMM of 16·T rows in the conv's operand mode, apart from the transforms
+    wp, wn, s = work.data_ptr(), work.numel(), stream()
+    v_el, m_el = nc * tiles * cin, nc * tiles * cout
+    f = f"sp_winograd_f{wm}3"
+    nres = bool(d.res1 or d.res1_bf16) + bool(d.res2 or d.res2_bf16)
+    return [("wino_tf", f + "_input", (C.byref(d), wp, wn, s), 0, 4 * (n * h * w * cin + v_el), (m, cin, "in")),
+            ("conv", f + "_gemm", (C.byref(d), planes.data_ptr(), planes.shape[1], wp, wn, s),
+             2 * nc * tiles * cout * cin, 4 * (v_el + m_el) + 2 * planes.numel(),
+             (nc * tiles, cout, cin, 1, 1, PREC_TAG[d.precision], "wino", m)),
+            ("wino_tf", f + "_output", (C.byref(d), wp, wn, s), 0, 4 * (m_el + m * cout * (1 + nres)),
+             (m, cout, "out"))]
+
+
+def wino_launch(stages, only=None):
+    """Launch wino_desc's stages in order; only = "input" | "gemm" | "output" launches that stage alone (tests:
+    the workspace then holds whatever the caller put there for it)."""
+    for st in stages:
+        if only is None or st[1].endswith("_" + only):
+            _launch(*st)
+
+
+def wino_plan(desc, wm: int, plane_stride: int | None = None, work_elems: int | None = None) -> dict:
+    """What the Winograd stages would run for an SpConvDesc under this thread's overrides (sp_winograd_plan: no
+    device call): {"gemm": conv_plan's dict of the batched component GEMM, "components", "in_vw", "out_vw",
+    "tiles"}. plane_stride / work_elems default to the exact sizes. Raises with the stages' message where they
+    would fail."""
+    from ._lib import SpConvPlanInfo, SpWinogradPlanInfo, call
+
+    nc = (wm + 2) ** 2
+    tiles = desc.N * ((desc.H + wm - 1) // wm) * ((desc.W + wm - 1) // wm)
+    ps = nc * desc.Cout * desc.Cin if plane_stride is None else plane_stride
+    we = wino_work_elems(wm, tiles, desc.Cin, desc.Cout) if work_elems is None else work_elems
+    info = SpWinogradPlanInfo()
+    call("sp_winograd_plan", C.byref(desc), int(wm), int(ps), int(we), C.byref(info))
+    out = {f: getattr(info, f) for f in ("components", "in_vw", "out_vw", "tiles")}
+    out["gemm"] = {f: getattr(info.gemm, f) for f, _ in SpConvPlanInfo._fields_}
+    return out
 
 
 def linear(x: V, rows: int, k: int, wt: torch.Tensor, n: int, out: V, *, bias=None, act=None,

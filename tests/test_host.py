@@ -80,7 +80,7 @@ def test_ctypes_descriptors_match_the_header_layout(tmp_path):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     structs = {"sp_conv_desc": _lib.SpConvDesc, "sp_msda_desc": _lib.SpMsdaDesc,
-               "sp_conv_plan_info": _lib.SpConvPlanInfo}
+               "sp_conv_plan_info": _lib.SpConvPlanInfo, "sp_winograd_plan_info": _lib.SpWinogradPlanInfo}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "spotter_hip.h"', "int main(void) {"]
     for cname, py in structs.items():
         lines.append(f'  printf("{cname} sizeof %zu\\n", sizeof({cname}));')

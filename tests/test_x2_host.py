@@ -175,9 +175,9 @@ def test_header_and_binding_agree_on_the_new_precision():
     from spotter_amd import _lib, ops
 
     hdr = open(os.path.join(ROOT, "include", "spotter_hip.h")).read()
-    assert re.search(r"SP_PREC_F32X2\s*=\s*3\b", hdr) and re.search(r"#define SP_ABI_VERSION 19\b", hdr)
+    assert re.search(r"SP_PREC_F32X2\s*=\s*3\b", hdr) and re.search(r"#define SP_ABI_VERSION 20\b", hdr)
     assert re.search(r"SP_CONV_GLDS\s*=\s*%d\b" % SP_CONV_GLDS, hdr)
-    assert _lib.ABI_VERSION == 19 and _lib.load().sp_abi_version() == 19
+    assert _lib.ABI_VERSION == 20 and _lib.load().sp_abi_version() == 20
     assert ops.PREC_BY_PLANES == {1: SP_PREC_BF16, 3: SP_PREC_F32X3, 2: SP_PREC_F32X2}
     assert ops.PREC_TAG[SP_PREC_F32X2] == "x2"
 

@@ -272,7 +272,7 @@ int sp_nchw_to_nhwc(const float* x, float* y, int n, int c, int h, int w, void* 
 /* Backbone stem conv 1 (RN:71-114: 3x3 stride 2 pad 1, Cin 3, FrozenBN affine M2:748-758, ReLU)
  * read directly from NCHW pixel_values x [n,3,h,w]; wt [cout][27] in (kh, kw, ci) order; y NHWC
  * [n, (h-1)/2+1, (w-1)/2+1, cout]. Replaces sp_nchw_to_nhwc + sp_conv2d for this layer. cout 32 or 64,
- * act 0 (none) or 1 (relu). (ABI v6) */
+ * act 0 (none) or 1 (relu); y 16-byte aligned (8 for the bf16 form). (ABI v6) */
 int sp_stem_conv3x3s2_nchw(const float* x, const float* wt, const float* scale, const float* shift, float* y,
                            int n, int h, int w, int cout, int act, void* stream);
 /* The same with bf16 output rows (ABI v10: the bf16 variant; fp32 arithmetic, RNE at the store). */
@@ -289,7 +289,7 @@ int sp_conv3x3_c32_bf16(const uint16_t* x, const uint16_t* w16, const float* sca
 int sp_conv3x3_c32(const float* x, const float* wt, const float* scale, const float* shift, float* y, int n, int h,
                    int w, int cout, int act, void* stream);
 /* The ResNet stage-0 3x3 (Cin 64 → Cout 64, stride 1 pad 1, RN:170-231) on bf16 rows (the bf16 variant):
- * bf16 [64][3][3][64] weights, rows ldx (% 8) / ldy (% 4)
+ * bf16 [64][3][3][64] weights, rows ldx / ldy (both % 8, >= 64, 16-byte aligned)
  * elements apart, fp32 accumulate, BN (+ the optional pre-activation residual res, bf16 rows ldr apart: the
  * basic block's shortcut, RN:170-200) + act in fp32, RNE at the store. */
 int sp_conv3x3_c64_bf16(const uint16_t* x, int64_t ldx, const uint16_t* w16, const float* scale, const float* shift,
@@ -306,11 +306,14 @@ int sp_conv3x3_c64_x3(const float* x, int64_t ldx, const uint16_t* w_planes, int
 int sp_conv3x3_c32_x3(const float* x, const uint16_t* w_planes, int64_t plane_stride, const float* scale,
                       const float* shift, float* y, int n, int h, int w, int cout, int act, void* stream);
 /* nn.MaxPool2d(3, 2, 1) on NHWC (RN:88). y rows are ldy floats apart (ldy >= c, ldy % 4 == 0), so the
- * result can land in a channel slice of a wider buffer (the fused bottleneck shortcut, ABI v6). */
+ * result can land in a channel slice of a wider buffer (the fused bottleneck shortcut, ABI v6). x and y 16-byte
+ * aligned, c % 4 == 0. NaN inputs are outside the contract: the maxima are fmaxf's, which drops a NaN operand
+ * where PyTorch propagates it. */
 int sp_maxpool3x3s2(const float* x, float* y, int64_t ldy, int n, int h, int w, int c, void* stream);
 /* The same on bf16 rows (ABI v10: the bf16 variant's backbone maps); c % 8 == 0, ldy % 8 == 0. */
 int sp_maxpool3x3s2_bf16(const uint16_t* x, uint16_t* y, int64_t ldy, int n, int h, int w, int c, void* stream);
-/* nn.AvgPool2d(2, 2, 0, ceil_mode=True) on NHWC (RN:150, RN:202); y rows ldy floats apart as above. */
+/* nn.AvgPool2d(2, 2, 0, ceil_mode=True) on NHWC (RN:150, RN:202); y rows ldy floats apart as above, x and y
+ * 16-byte aligned. fp32 sum in (dy, dx) order divided by the in-map count. */
 int sp_avgpool2x2_ceil(const float* x, float* y, int64_t ldy, int n, int h, int w, int c, void* stream);
 /* The same on bf16 rows (ABI v10; fp32 sum and divide, RNE to bf16); c % 8 == 0, ldy % 8 == 0. */
 int sp_avgpool2x2_ceil_bf16(const uint16_t* x, uint16_t* y, int64_t ldy, int n, int h, int w, int c, void* stream);

@@ -456,7 +456,7 @@ extern "C" int sp_nchw_to_nhwc(const float* x, float* y, int n, int c, int h, in
 
 extern "C" int sp_maxpool3x3s2(const float* x, float* y, int64_t ldy, int n, int h, int w, int c, void* stream) {
   SP_ARG_CHECK(x && y && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0 && ldy >= c && ldy % 4 == 0 &&
-                   ((uintptr_t)y & 15) == 0,
+                   ((uintptr_t)y & 15) == 0 && ((uintptr_t)x & 15) == 0,
                "sp_maxpool3x3s2: bad args");
   int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
   SP_ARG_CHECK((int64_t)n * ho < (1 << 30) && (int64_t)wo * (c / 4) < (1 << 30), "sp_maxpool3x3s2: size out of range");
@@ -472,7 +472,7 @@ extern "C" int sp_maxpool3x3s2(const float* x, float* y, int64_t ldy, int n, int
 extern "C" int sp_avgpool2x2_ceil(const float* x, float* y, int64_t ldy, int n, int h, int w, int c,
                                   void* stream) {
   SP_ARG_CHECK(x && y && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0 && ldy >= c && ldy % 4 == 0 &&
-                   ((uintptr_t)y & 15) == 0,
+                   ((uintptr_t)y & 15) == 0 && ((uintptr_t)x & 15) == 0,
                "sp_avgpool2x2_ceil: bad args");
   int ho = (h + 1) / 2, wo = (w + 1) / 2;
   SP_ARG_CHECK((int64_t)n * ho < (1 << 30) && (int64_t)wo * (c / 4) < (1 << 30), "sp_avgpool2x2_ceil: size out of range");

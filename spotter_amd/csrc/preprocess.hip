@@ -379,8 +379,9 @@ extern "C" int sp_preprocess_u8(const sp_image_u8* images, int n, int out_h, int
     bool same = out_w % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
     for (int i = 0; i < cnt && same; ++i) {
       const sp_image_u8& im = images[base + i];
+      // a row_stride below 3·width is left to the generic path, which refuses it
       same = im.data && im.height == out_h && im.width == out_w && im.row_stride % 4 == 0 &&
-             (reinterpret_cast<uintptr_t>(im.data) & 3) == 0;
+             im.row_stride >= 3 * im.width && (reinterpret_cast<uintptr_t>(im.data) & 3) == 0;
     }
     if (same) {  // every source already has the output size: rescale + CHW only
       for (int i = 0; i < cnt; ++i) {

@@ -112,6 +112,8 @@ int stem_launch(const char* what, const float* x, const float* wt, const float* 
   SP_ARG_CHECK(x && wt && scale && shift && y && n > 0 && h > 0 && w > 0 && (act == 0 || act == 1) &&
                    (cout == 32 || cout == 64),
                "%s: bad args (cout must be 32 or 64, act none/relu)", what);
+  // the workgroup's rows leave as float4 (fp32 rows) / uint2 (bf16 rows) stores
+  SP_ARG_CHECK(((uintptr_t)y & (4 * sizeof(OT) - 1)) == 0, "%s: y must be %d-byte aligned", what, (int)(4 * sizeof(OT)));
   const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
   const int64_t total = (int64_t)n * ho * wo;
   const unsigned grid = (unsigned)((total + STEM_BLOCK - 1) / STEM_BLOCK);

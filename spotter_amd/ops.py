@@ -684,15 +684,16 @@ def box_refine(delta: V, ref: torch.Tensor, rows):
 
 
 def preprocess_u8(images, out: torch.Tensor, out_h: int, out_w: int):
-    """images: list of uint8 CUDA tensors [H, W, 3] (contiguous)."""
+    """images: list of uint8 CUDA tensors [H, W, 3], contiguous or row views of a wider buffer (packed pixels,
+    rows im.stride(0) >= 3·W bytes apart: sp_image_u8.row_stride)."""
     n = len(images)
     arr = (SpImageU8 * n)()
     for i, im in enumerate(images):
         assert im.dtype == torch.uint8 and im.is_cuda and im.dim() == 3 and im.shape[2] == 3
-        assert im.is_contiguous()
+        assert im.stride(2) == 1 and im.stride(1) == 3 and (im.shape[0] == 1 or im.stride(0) >= 3 * im.shape[1])
         arr[i].data = im.data_ptr()
         arr[i].height, arr[i].width = im.shape[0], im.shape[1]
-        arr[i].row_stride = im.shape[1] * 3
+        arr[i].row_stride = im.stride(0) if im.shape[0] > 1 else im.shape[1] * 3
     assert out.numel() >= n * 3 * out_h * out_w and out.dtype == torch.float32
     nbytes = sum(int(im.numel()) for im in images) + 4 * n * 3 * out_h * out_w
     _launch("preprocess", "sp_preprocess_u8", (arr, n, out_h, out_w, out.data_ptr(), stream()), 0, nbytes,

@@ -503,6 +503,40 @@ int sp_draw_pack(const sp_draw_op* ops, int32_t n_ops, const uint8_t* masks, int
 int sp_draw_rgb(uint8_t* rgb, int32_t height, int32_t width, int64_t row_stride, const void* table_host,
                 const void* table_dev, int64_t table_bytes, void* stream);
 
+/*
+ * Cross-process batching (spotter_amd/shared_batch.py): the replica processes of one GPU hand their images to
+ * one engine owner through host shared memory. Additive to ABI v20.
+ *
+ * sp_host_register pins `bytes` of page-aligned (4096) host memory, e.g. a POSIX shared-memory mapping, and
+ * returns in *dev_ptr the address kernels use for it; sp_host_unregister releases it. Refused with a message and
+ * a non-zero status, nothing changed: p NULL, dev_ptr NULL, bytes <= 0, p not page aligned, a range that
+ * overlaps a registered one, an unregister of memory that is not registered.
+ */
+int sp_host_register(void* p, int64_t bytes, void** dev_ptr);
+int sp_host_unregister(void* p);
+
+/* ONE launch that copies n independent fp32 segments (bit patterns kept: NaN payloads, -0.0). src / dst are
+ * device memory or the device pointer of registered host memory, 4-byte aligned; the ranges of one call must
+ * not overlap. A segment whose src and dst share their offset from 16-byte alignment moves as 16-byte vectors
+ * between a scalar head and tail, any other as 4-byte words. A workgroup copies SP_COPY_BLOCK_ELEMS elements
+ * of one segment; which segment a workgroup serves is computed on the host into the kernel's by-value
+ * argument, so the call uploads nothing, allocates nothing and can be captured in a graph. elems == 0 segments
+ * are skipped. Refused with -1 and nothing launched: d NULL, n outside [1, SP_COPY_MAX_SEGMENTS], elems < 0,
+ * a NULL or misaligned pointer with elems > 0, more than 2^31 - 1 workgroups. */
+#define SP_COPY_MAX_SEGMENTS 64
+#define SP_COPY_BLOCK_ELEMS 4096
+typedef struct {
+  const float* src;
+  float* dst;
+  int64_t elems;
+} sp_copy_segment;
+typedef struct {
+  int32_t n;
+  int32_t reserved;
+  sp_copy_segment seg[SP_COPY_MAX_SEGMENTS];
+} sp_copy_segments_desc;
+int sp_copy_segments(const sp_copy_segments_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

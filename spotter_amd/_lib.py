@@ -109,6 +109,17 @@ class SpDrawTable(C.Structure):
     ]
 
 
+SP_COPY_MAX_SEGMENTS, SP_COPY_BLOCK_ELEMS = 64, 4096
+
+
+class SpCopySegment(C.Structure):
+    _fields_ = [("src", vp), ("dst", vp), ("elems", i64)]
+
+
+class SpCopySegmentsDesc(C.Structure):
+    _fields_ = [("n", i32), ("reserved", i32), ("seg", SpCopySegment * SP_COPY_MAX_SEGMENTS)]
+
+
 SP_DRAW_FILL, SP_DRAW_BLEND = 0, 1  # sp_draw_kind
 SP_DRAW_TILE_W, SP_DRAW_TILE_H = 64, 8
 SP_JPEG_UNSUPPORTED = -10
@@ -170,6 +181,9 @@ _SIGS = {
     "sp_jpeg_enc_finish": (i32, [C.POINTER(SpJpegEncLayout), vp, i64, vp, i64, vp, i64, C.POINTER(i64)]),
     "sp_draw_pack": (i32, [vp, i32, vp, i64, i32, i32, vp, i64, C.POINTER(i64)]),
     "sp_draw_rgb": (i32, [vp, i32, i32, i64, vp, vp, i64, vp]),
+    "sp_host_register": (i32, [vp, i64, C.POINTER(vp)]),
+    "sp_host_unregister": (i32, [vp]),
+    "sp_copy_segments": (i32, [C.POINTER(SpCopySegmentsDesc), vp]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -16,6 +16,7 @@ from dataclasses import dataclass
 import torch
 
 from .config import PRESETS, SpotterConfig, check_precision
+from .shared_batch import batching_from_env, check_batching, default_socket
 
 
 @dataclass
@@ -50,12 +51,19 @@ class SpotterForObjectDetection:
     main_input_name = "pixel_values"
 
     def __init__(self, cfg: SpotterConfig, weights: dict | None = None, seed: int = 0,
-                 use_graphs: bool = True, precision: str = "fp32", batching: bool = False,
+                 use_graphs: bool = True, precision: str = "fp32", batching: bool | str = False,
                  max_batch: int = 32, max_wait_ms: float = 2.0):
-        """batching: coalesce concurrent calls (several request threads) into one engine forward
-        (spotter_amd.batching.MicroBatcher, up to max_batch images within max_wait_ms)."""
+        """batching: True or "threads" coalesces concurrent calls (several request threads) into one engine forward
+        (spotter_amd.batching.MicroBatcher, up to max_batch images within max_wait_ms); "shared" hands every call to
+        the one engine owner process of this GPU (spotter_amd.shared_batch), which coalesces the calls of all the
+        replica processes on it: this object then builds no engine. False or "off": neither. Anything else raises
+        ValueError here, at construction."""
         self.cfg = cfg
-        self.batching = batching
+        self.batching = check_batching(batching)
+        self._shared = None
+        self._shared_opts = {}  # SharedBatchClient keywords (tests: stub, timeouts)
+        self._name = None  # what from_pretrained was given: the name a shared-batch owner loads
+        self._revision = None
         self.max_batch = max_batch
         self.max_wait_ms = max_wait_ms
         self._batcher = None
@@ -83,18 +91,26 @@ class SpotterForObjectDetection:
         `synthetic=True`, or a name of the form "synthetic:<preset>" (e.g. via MODEL_NAME).
         precision: the engine's operand precision (config.PRECISIONS); the drop-in serve.py passes
         os.environ.get("SPOTTER_PRECISION", "fp32") (deploy/rayservice-template.yaml sets "bf16" for C4).
-        HF's own from_pretrained has no such input; the weights loaded are the same either way."""
+        HF's own from_pretrained has no such input; the weights loaded are the same either way.
+        batching: as the constructor's; when it is not given, the SPOTTER_BATCHING environment variable (off,
+        threads or shared) decides, so a deployment turns batching on without a change to serve.py."""
         check_precision(precision)
         kw["precision"] = precision
+        if "batching" not in kw:
+            kw["batching"] = batching_from_env()
         if name_or_path.startswith("synthetic:"):
             synthetic, name_or_path = True, name_or_path[len("synthetic:"):]
         if synthetic:
             preset = name_or_path if name_or_path in PRESETS else _preset_for(name_or_path).name
-            return cls(PRESETS[preset], None, **kw)
+            m = cls(PRESETS[preset], None, **kw)
+            m._name = f"synthetic:{preset}"
+            return m
         from .checkpoint import load_local, resolve_pretrained
 
         cfg, weights = load_local(resolve_pretrained(name_or_path, revision=revision))
-        return cls(cfg, weights, **{k: v for k, v in kw.items() if k != "seed"})
+        m = cls(cfg, weights, **{k: v for k, v in kw.items() if k != "seed"})
+        m._name, m._revision = name_or_path, revision
+        return m
 
     def _host_weights(self):
         if self._weights is None:
@@ -117,6 +133,7 @@ class SpotterForObjectDetection:
         st = self.__dict__.copy()
         st["_engine"] = None
         st["_batcher"] = None
+        st["_shared"] = None  # the connection and the slot belong to this process
         st["_lock"] = None
         st["_graphs"] = {}
         st["_seen"] = set()
@@ -142,6 +159,9 @@ class SpotterForObjectDetection:
     def __call__(self, pixel_values=None, pixel_mask=None, **kwargs):
         if pixel_values is None:
             raise ValueError("You have to specify either pixel_values or inputs_embeds")
+        if getattr(self, "batching", False) == "shared":
+            logits, boxes = self._shared_client()(pixel_values)  # owned tensors on pixel_values' device
+            return SpotterDetectionOutput(logits=logits, pred_boxes=boxes)
         eng = self.engine
         if torch.is_tensor(pixel_values) and pixel_values.device != eng.dev:
             pixel_values = pixel_values.to(eng.dev)
@@ -157,6 +177,28 @@ class SpotterForObjectDetection:
         logits, boxes = self._run(pixel_values)
         # own copies: the engine reuses its workspace on the next call
         return SpotterDetectionOutput(logits=logits.clone(), pred_boxes=boxes.clone())
+
+    def _shared_client(self):
+        """The connection to this GPU's engine owner (batching="shared"); no engine is built in this process."""
+        if self._shared is None:
+            with self._lock:
+                if self._shared is None:
+                    from .shared_batch import MAX_BATCH_LIMIT, SharedBatchClient, weights_digest
+
+                    if self._device is not None and self._device.index is not None:
+                        idx = self._device.index
+                    else:
+                        idx = torch.cuda.current_device() if torch.cuda.is_available() else 0
+                    name = self._name
+                    if name is None and self._weights is None and self._seed == 0 and self.cfg.name in PRESETS \
+                            and PRESETS[self.cfg.name] == self.cfg:
+                        name = f"synthetic:{self.cfg.name}"  # what from_pretrained("synthetic:<preset>") builds
+                    opts = dict(max_batch=min(self.max_batch, MAX_BATCH_LIMIT), max_wait_ms=self.max_wait_ms)
+                    opts.update(getattr(self, "_shared_opts", {}))
+                    self._shared = SharedBatchClient(
+                        self.cfg, self.precision, name, lambda: weights_digest(self._host_weights()),
+                        default_socket(idx), device_index=idx, revision=getattr(self, "_revision", None), **opts)
+        return self._shared
 
     def _run(self, pixel_values):
         """One forward on the engine's stream; outputs live in engine / graph buffers until the next call."""

@@ -710,3 +710,29 @@ def postprocess(logits: torch.Tensor, boxes: torch.Tensor, target_hw: torch.Tens
     args = (logits.data_ptr(), boxes.data_ptr(), target_hw.data_ptr(), b, q, c, k, threshold, scores.data_ptr(),
             labels.data_ptr(), boxes_xyxy.data_ptr(), counts.data_ptr(), work.data_ptr(), stream())
     _launch("postprocess", "sp_postprocess", args, 0, 4 * b * (q * c + q * 4 + k * 7), (b, q, c, k))
+
+
+def copy_segments(segments, stream_handle: int | None = None):
+    """ONE launch copying every (src_ptr, dst_ptr, elems) fp32 segment (sp_copy_segments): the shared batcher's
+    gather and scatter. Pointers are device addresses (or sp_host_register's); the caller vouches for their spans."""
+    from ._lib import SP_COPY_MAX_SEGMENTS, SpCopySegmentsDesc
+
+    if not 1 <= len(segments) <= SP_COPY_MAX_SEGMENTS:
+        raise ValueError(f"copy_segments: {len(segments)} segments outside [1, {SP_COPY_MAX_SEGMENTS}]")
+    d = SpCopySegmentsDesc(n=len(segments))
+    for i, (src, dst, elems) in enumerate(segments):
+        d.seg[i].src, d.seg[i].dst, d.seg[i].elems = src, dst, elems
+    nbytes = 8 * sum(int(e) for _, _, e in segments)
+    _launch("elementwise", "sp_copy_segments", (C.byref(d), stream() if stream_handle is None else stream_handle),
+            0, nbytes)
+
+
+def host_register(addr: int, nbytes: int) -> int:
+    """Pin page-aligned host memory (e.g. a shared-memory mapping) for kernels; returns its device address."""
+    dev = C.c_void_p()
+    call("sp_host_register", addr, nbytes, C.byref(dev))
+    return int(dev.value)
+
+
+def host_unregister(addr: int):
+    call("sp_host_unregister", addr)

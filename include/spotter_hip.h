@@ -194,10 +194,7 @@ enum sp_conv_family {
   SP_CONV_FP32 = 0,      /* conv_gemm_kernel (fp32 MFMA) */
   SP_CONV_MFMA16 = 1,    /* conv_mfma16_kernel (register-staged, bf16 / split operands) */
   SP_CONV_GLDS = 2,      /* conv_glds_kernel (LDS-DMA) */
-  SP_CONV_PIPE = 3,      /* diagnostic builds: conv_pipe_kernel */
-  SP_CONV_PP = 4,        /* diagnostic builds: conv_pp_kernel */
-  SP_CONV_X3S = 5,       /* diagnostic builds: conv_x3s_kernel */
-  SP_CONV_X3P = 6,       /* diagnostic builds: conv_x3p_kernel */
+  /* 3-6: retired with the conv_pipe / conv_pp / conv_x3s / conv_x3p kernels; not reused */
   SP_CONV_FUSED_LN = 7,  /* diagnostic builds: conv_gemm_kernel with the row-LayerNorm epilogue */
 };
 typedef struct {

@@ -57,6 +57,13 @@ __device__ __forceinline__ float wave_max(float v) {
 // torch.sigmoid on fp32: 1 / (1 + exp(-x))
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// XCD-aware bijective remap of a 1-D grid: MI355X deals consecutive workgroups round-robin over the
+// 8 XCDs, so workgroup b runs on XCD b % 8; index v gives each XCD a contiguous run.
+__device__ __forceinline__ int xcd_index(int b, int nwg) {
+  const int xcd = b & 7, q8 = nwg >> 3, r8 = nwg & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
+}
+
 // A translation unit's bounds log (SP_BOUNDS builds): violations, and the first one's source line, index, extent.
 struct BoundsLog {
   unsigned int hits;

@@ -41,6 +41,95 @@ struct ConvArgs {
   int32_t* counters = nullptr;
 };
 
+// ---- Pieces the GEMM kernels share (conv_gemm.hip, conv_mfma16.hip, conv_glds.h).
+
+// Where accumulator element q of a 32×32 block sits for `lane`. v_mfma_f32_32x32x*: lane (r, h) holds rows
+// (q&3) + 8(q>>2) + 4h, column r. L16: the f32x16 holds 2×2 blocks of v_mfma_f32_16x16x32 results (element
+// q = 8·bi + 4·bj + reg; lane l holds rows 16bi + 4(l >> 4) + reg, column 16bj + (l & 15)); `slot` = bj, which
+// of the lane's two columns of the block (0 otherwise).
+struct AccPos {
+  int row, col, slot;
+};
+template <bool L16>
+__device__ __forceinline__ AccPos acc_pos(int q, int lane) {
+  if constexpr (L16) return {16 * (q >> 3) + 4 * (lane >> 4) + (q & 3), 16 * ((q >> 2) & 1) + (lane & 15), (q >> 2) & 1};
+  else return {(q & 3) + 8 * (q >> 2) + 4 * (lane >> 5), lane & 31, 0};
+}
+
+template <int TM, int TN>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+}
+
+// Origin (first row, first column) of BM × BN output tile `wg`, N fastest.
+struct TileOrigin {
+  int64_t m0;
+  int n0;
+};
+template <int BM, int BN>
+__device__ __forceinline__ TileOrigin tile_origin(const ConvArgs& p, int wg) {
+  const int tilesN = (p.d.Cout + BN - 1) / BN;
+  const int mt = wg / tilesN;
+  const int n0 = (wg - mt * tilesN) * BN;
+  return {(int64_t)mt * BM, n0};
+}
+
+// This workgroup's k-tiles [kt0, kt1) of nk_all under split-K (blockIdx.z of p.splits).
+struct KRange {
+  int kt0, kt1;
+};
+__device__ __forceinline__ KRange splitk_range(const ConvArgs& p, int nk_all) {
+  return {(int)(((int64_t)nk_all * blockIdx.z) / p.splits), (int)(((int64_t)nk_all * (blockIdx.z + 1)) / p.splits)};
+}
+
+// Implicit im2col, output row m: the input coordinates (iy0, ix0) of its filter tap (0,0) and that tap's pixel
+// index in the NHWC activations. Rows past M are parked out of bounds (iy0 = -2^20), so every tap's range
+// check fails for them.
+struct Im2colRow {
+  int iy0, ix0;
+  int64_t pix;
+};
+__device__ __forceinline__ Im2colRow im2col_row(const ConvArgs& p, int64_t m) {
+  const sp_conv_desc& d = p.d;
+  const bool ok = m < p.M;
+  const int64_t mm = ok ? m : 0;
+  const int b = (int)(mm / p.HoWo);
+  const int rem = (int)(mm - (int64_t)b * p.HoWo);
+  const int oy = rem / d.Wo;
+  const int ox = rem - oy * d.Wo;
+  SP_BCHECK(b, d.N);
+  const int iy0 = ok ? oy * d.stride - d.pad : -(1 << 20);
+  const int ix0 = ox * d.stride - d.pad;
+  return {iy0, ix0, ((int64_t)b * d.H + iy0) * d.W + ix0};
+}
+
+// The filter-tap walk of the Cin % BK == 0 kernels: a k-tile lies inside one tap, so (kh, kw, c0) is
+// wave-uniform scalar state, set once and advanced by one k-tile per step.
+struct TapWalk {
+  int kh = 0, kw = 0, c0 = 0;
+  __device__ __forceinline__ void seek(const sp_conv_desc& d, int k0) {
+    const int tap = k0 / d.Cin;
+    c0 = k0 - tap * d.Cin;
+    kh = tap / d.KW;
+    kw = tap - kh * d.KW;
+  }
+  __device__ __forceinline__ void advance(const sp_conv_desc& d, int bk) {
+    c0 += bk;
+    if (c0 >= d.Cin) {
+      c0 = 0;
+      if (++kw == d.KW) {
+        kw = 0;
+        ++kh;
+      }
+    }
+  }
+};
+
 // Output row offset (elements): plain row-major (out_rows_per_group == 0) or grouped rows.
 __device__ __forceinline__ int64_t out_off(const sp_conv_desc& d, int64_t m) {
   if (d.out_rows_per_group <= 0) return m * d.ldc;
@@ -166,19 +255,19 @@ __device__ __forceinline__ void store_partial(const ConvArgs& p, int64_t m, int 
     *reinterpret_cast<float4*>(p.partial + e) = v;
 }
 
-// Accumulator band i of a wave (TN 32x32 MFMA tiles, v_mfma_f32_32x32x*: lane (r, h) holds
-// rows (q&3) + 8(q>>2) + 4h, column r) → the wave's private LDS slab → fused epilogue on
-// float4s of one output row (or raw partial sums for split-K).
+// Accumulator band i of a wave (TN 32x32 MFMA tiles, acc_pos layout) → the wave's private LDS slab → fused
+// epilogue on float4s of one output row (or raw partial sums for split-K).
 template <int TN, bool BF = false, bool CNT = false>
 __device__ __forceinline__ void epilogue_band(const ConvArgs& p, float* slab, const f32x16* accrow,
                                               int64_t mb, int nb, int lane) {
   constexpr int WN = TN * 32;
-  const int r = lane & 31;
-  const int h = lane >> 5;
 #pragma unroll
   for (int j = 0; j < TN; ++j)
 #pragma unroll
-    for (int q = 0; q < 16; ++q) slab[((q & 3) + 8 * (q >> 2) + 4 * h) * WN + j * 32 + r] = accrow[j][q];
+    for (int q = 0; q < 16; ++q) {
+      const AccPos a = acc_pos<false>(q, lane);
+      slab[a.row * WN + j * 32 + a.col] = accrow[j][q];
+    }
   __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes done
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -203,8 +292,7 @@ __device__ __forceinline__ void epilogue_band(const ConvArgs& p, float* slab, co
 // then the fused epilogue on float4s of one output row, with the res1 loads of G consecutive
 // tasks issued before their stores so the residual fetch latency overlaps. NB = TM when the
 // region fits in the operand stages' LDS, else 1 (band by band).
-// L16: the f32x16 of each 32×32 block holds 2×2 blocks of v_mfma_f32_16x16x32 results (element
-// q = 8·bi + 4·bj + reg; lane l holds rows 16bi + 4(l >> 4) + reg, column 16bj + (l & 15)).
+// L16: the f32x16 of each 32×32 block holds 2×2 blocks of v_mfma_f32_16x16x32 results (acc_pos).
 template <int TM, int TN, int NB, bool L16 = false, bool BF = false, bool CNT = false>
 __device__ __forceinline__ void epilogue_tile(const ConvArgs& p, float* region, f32x16 (*acc)[TN],
                                               int64_t mb, int nb, int lane) {
@@ -213,8 +301,6 @@ __device__ __forceinline__ void epilogue_tile(const ConvArgs& p, float* region, 
   constexpr int PER = NB * (32 * WN / 4) / 64;  // float4 tasks per lane per round
   constexpr int G = PER < 4 ? PER : 4;
   static_assert(PER % G == 0, "task groups");
-  const int r = lane & 31;
-  const int h = lane >> 5;
   const sp_conv_desc& d = p.d;
   const bool fastv = p.vec_epi && p.splits == 1;
 #pragma unroll
@@ -226,9 +312,8 @@ __device__ __forceinline__ void epilogue_tile(const ConvArgs& p, float* region, 
       for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const int rr = L16 ? 16 * (q >> 3) + 4 * (lane >> 4) + (q & 3) : (q & 3) + 8 * (q >> 2) + 4 * h;
-          const int cc = L16 ? 16 * ((q >> 2) & 1) + (lane & 15) : r;
-          region[(i * 32 + rr) * WN + j * 32 + cc] = acc[i0 + i][j][q];
+          const AccPos a = acc_pos<L16>(q, lane);
+          region[(i * 32 + a.row) * WN + j * 32 + a.col] = acc[i0 + i][j][q];
         }
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
     __builtin_amdgcn_wave_barrier();
@@ -345,12 +430,13 @@ __device__ __forceinline__ void epilogue_rowln(const ConvArgs& p, float* tile, c
   constexpr int BN = 128 * TN;
   constexpr int LDT = BN + 4;
   constexpr int PER = BN / 64;
-  const int r = lane & 31;
-  const int h = lane >> 5;
 #pragma unroll
   for (int j = 0; j < TN; ++j)
 #pragma unroll
-    for (int q = 0; q < 16; ++q) tile[((q & 3) + 8 * (q >> 2) + 4 * h) * LDT + wave * 32 * TN + j * 32 + r] = acc[j][q];
+    for (int q = 0; q < 16; ++q) {
+      const AccPos a = acc_pos<false>(q, lane);
+      tile[a.row * LDT + wave * 32 * TN + j * 32 + a.col] = acc[j][q];
+    }
   __syncthreads();
   const sp_conv_desc& d = p.d;
   const int N = d.Cout;

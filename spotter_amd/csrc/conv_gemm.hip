@@ -161,17 +161,11 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvArgs p) {
   const int h = lane >> 5;
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+  zero_acc(acc);
 
-  const int nk_all = (p.K + BK - 1) / BK;
-  const int kt0 = (int)(((int64_t)nk_all * blockIdx.z) / p.splits);
-  const int kt1 = (int)(((int64_t)nk_all * (blockIdx.z + 1)) / p.splits);
-  const int nk = kt1 - kt0;
+  const KRange kr = splitk_range(p, (p.K + BK - 1) / BK);
+  const int kt0 = kr.kt0;
+  const int nk = kr.kt1 - kt0;
 
   auto store_tile = [&](float* st) {
     float* As = st;

@@ -38,10 +38,6 @@ __device__ unsigned long long g_glds_stamps[16384 * 6];
 #ifndef SP_EPI16_C8
 #define SP_EPI16_C8 1
 #endif
-// -DSP_EPI16_PAIRS=1: its LDS element pass on 4-byte column pairs (DPP swap): measured mixed, off
-#ifndef SP_EPI16_PAIRS
-#define SP_EPI16_PAIRS 0
-#endif
 
 namespace {
 
@@ -70,10 +66,9 @@ __device__ __forceinline__ void glds_main(const ConvArgs& p, uint4* smem, int wg
   const int wave = tid >> 6;
   const int lane = tid & 63;
 
-  const int tilesN = (d.Cout + BN - 1) / BN;
-  const int mt = wg / tilesN;
-  const int n0 = (wg - mt * tilesN) * BN;
-  const int64_t m0 = (int64_t)mt * BM;
+  const TileOrigin org = tile_origin<BM, BN>(p, wg);
+  const int64_t m0 = org.m0;
+  const int n0 = org.n0;
   // the grid matches the problem: every tile starts inside M × Cout, k-tiles inside K, batch member inside batch
   SP_BCHECK(m0, p.M);
   SP_BCHECK(n0, d.Cout);
@@ -100,17 +95,10 @@ __device__ __forceinline__ void glds_main(const ConvArgs& p, uint4* smem, int wg
   const char* a_ptr[GAP];
 #pragma unroll
   for (int j = 0; j < GAP; ++j) {
-    const int64_t m = m0 + (j * NT + tid) / RA;
-    const bool ok = m < p.M;
-    const int64_t mm = ok ? m : 0;
-    const int b = (int)(mm / p.HoWo);
-    const int rem = (int)(mm - (int64_t)b * p.HoWo);
-    const int oy = rem / d.Wo;
-    const int ox = rem - oy * d.Wo;
-    SP_BCHECK(b, d.N);
-    a_iy0[j] = ok ? oy * d.stride - d.pad : -(1 << 20);
-    a_ix0[j] = ox * d.stride - d.pad;
-    a_ptr[j] = A + (((int64_t)b * d.H + a_iy0[j]) * d.W + a_ix0[j]) * d.lda * ES + ca * 16;
+    const Im2colRow row = im2col_row(p, m0 + (j * NT + tid) / RA);
+    a_iy0[j] = row.iy0;
+    a_ix0[j] = row.ix0;
+    a_ptr[j] = A + row.pix * d.lda * ES + ca * 16;
   }
   const uint16_t* b_ptr[GB];
   bool b_ok[GB];
@@ -138,15 +126,9 @@ __device__ __forceinline__ void glds_main(const ConvArgs& p, uint4* smem, int wg
     }
   }
 
-  int s_kh = 0, s_kw = 0, s_c0 = 0;
+  TapWalk walk;
   const int nk = kt1 - kt0;
-  {
-    const int k0 = kt0 * BK;
-    const int tap = k0 / d.Cin;
-    s_c0 = k0 - tap * d.Cin;
-    s_kh = tap / d.KW;
-    s_kw = tap - s_kh * d.KW;
-  }
+  walk.seek(d, kt0 * BK);
 
   // Issue the DMA pieces of k-tile kt into stage buffer `buf`, then advance the tap walk.
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint4*)smem;
@@ -168,13 +150,13 @@ __device__ __forceinline__ void glds_main(const ConvArgs& p, uint4* smem, int wg
       }
       return;
     }
-    const int64_t off = (((int64_t)s_kh * d.W + s_kw) * d.lda + s_c0) * ES;
+    const int64_t off = (((int64_t)walk.kh * d.W + walk.kw) * d.lda + walk.c0) * ES;
     // the tap walk stays inside the filter and each A piece's channels inside Cin (≤ lda)
-    SP_BCHECK(s_kh, d.KH);
-    SP_BCHECK(s_c0 + (ca + 1) * (16 / ES) - 1, d.Cin);
+    SP_BCHECK(walk.kh, d.KH);
+    SP_BCHECK(walk.c0 + (ca + 1) * (16 / ES) - 1, d.Cin);
 #pragma unroll
     for (int j = 0; j < GAP; ++j) {
-      const bool ok = (unsigned)(a_iy0[j] + s_kh) < (unsigned)d.H && (unsigned)(a_ix0[j] + s_kw) < (unsigned)d.W;
+      const bool ok = (unsigned)(a_iy0[j] + walk.kh) < (unsigned)d.H && (unsigned)(a_ix0[j] + walk.kw) < (unsigned)d.W;
 #pragma unroll
       for (int pl = 0; pl < NAP; ++pl) {
         const void* src = ok ? static_cast<const void*>(a_ptr[j] + pl * aps + off)
@@ -192,14 +174,7 @@ __device__ __forceinline__ void glds_main(const ConvArgs& p, uint4* smem, int wg
                                   : static_cast<const void*>(zero + cbk * 16);
         glds16(src, st + (CA + pl * CB + j * NT) * 16);
       }
-    s_c0 += BK;
-    if (s_c0 >= d.Cin) {
-      s_c0 = 0;
-      if (++s_kw == d.KW) {
-        s_kw = 0;
-        ++s_kh;
-      }
-    }
+    walk.advance(d, BK);
   };
 
   const int wm = wave / WN;
@@ -312,12 +287,7 @@ __device__ __forceinline__ void glds_main(const ConvArgs& p, uint4* smem, int wg
 
 template <int TM, int TN, bool M16>
 __device__ __forceinline__ void glds_zero(f32x16 (&acc)[TM][TN], f32x4 (&acc4)[M16 ? 2 * TM : 1][M16 ? 2 * TN : 1]) {
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+  zero_acc(acc);
   if constexpr (M16) {
 #pragma unroll
     for (int i = 0; i < 2 * TM; ++i)
@@ -342,7 +312,7 @@ __device__ __forceinline__ void epilogue_tile_rd(const ConvArgs& p, float* regio
   constexpr int NI = NB * 32 * C4 / 64;    // 1 KB DMA pieces (and float4 store tasks) per lane per round
   constexpr int NCOL = L16 ? 2 : 1;        // distinct accumulator columns of a lane per 32-wide block
   const sp_conv_desc& d = p.d;
-  const int r = lane & 31, h = lane >> 5;
+  const int r = lane & 31;
   float scv[TN][NCOL], shv[TN][NCOL];
 #pragma unroll
   for (int j = 0; j < TN; ++j)
@@ -378,9 +348,8 @@ __device__ __forceinline__ void epilogue_tile_rd(const ConvArgs& p, float* regio
       for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const int rr = L16 ? 16 * (q >> 3) + 4 * (lane >> 4) + (q & 3) : (q & 3) + 8 * (q >> 2) + 4 * h;
-          const int cc = L16 ? 16 * ((q >> 2) & 1) + (lane & 15) : r;
-          const int k = L16 ? (q >> 2) & 1 : 0;
+          const AccPos ap = acc_pos<L16>(q, lane);
+          const int rr = ap.row, cc = ap.col, k = ap.slot;
           float* slot = region + (i * 32 + rr) * WN + j * 32 + cc;
           float v = fmaf(acc[i0 + i][j][q], scv[j][k], shv[j][k]);
           if (res) v += *slot;
@@ -456,6 +425,8 @@ __device__ __forceinline__ void epilogue_tile_rdd(const ConvArgs& p, float* regi
     }
   };
   if (res) fetch(mb);
+  // the accumulator map is written out twice below: with acc_pos the store offsets were selected differently
+  // (+93 … +209 instructions per variant 4 kernel, profiles/conv_share/isa_compare.md)
 #pragma unroll
   for (int i0 = 0; i0 < TM; i0 += NB) {
     float o[NB][TN][16];
@@ -508,7 +479,7 @@ __device__ __forceinline__ void epilogue_tile_rd16(const ConvArgs& p, float* reg
   constexpr int NCOL = L16 ? 2 : 1;
   static_assert(NI * 64 * 8 == NB * 32 * WN && NQ * 64 * 4 == NB * 32 * WN, "slab pieces");
   const sp_conv_desc& d = p.d;
-  const int r = lane & 31, h = lane >> 5;
+  const int r = lane & 31;
   float scv[TN][NCOL], shv[TN][NCOL];
 #pragma unroll
   for (int j = 0; j < TN; ++j)
@@ -542,49 +513,19 @@ __device__ __forceinline__ void epilogue_tile_rd16(const ConvArgs& p, float* reg
       glds16(src, rbase + u * 1024);
     }
     if (res) wait_vmcnt<0>();
-#if SP_EPI16_PAIRS
-    // Lanes l and l ^ 1 hold adjacent columns of the same rows, and elements q, q + 1 (q even) adjacent rows:
-    // one DPP swap per element pair gives the even lane row rr (columns cc, cc + 1) and the odd lane row rr + 1
-    // (columns cc - 1, cc), so the residual is read and the output written as 4-byte pairs.
-    const bool odd = lane & 1;
-#pragma unroll
-    for (int i = 0; i < NB; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int q = 0; q < 16; q += 2) {
-          const int rr = L16 ? 16 * (q >> 3) + 4 * (lane >> 4) + (q & 3) : (q & 3) + 8 * (q >> 2) + 4 * h;
-          const int cc = L16 ? 16 * ((q >> 2) & 1) + (lane & 15) : r;
-          const int k = L16 ? (q >> 2) & 1 : 0;
-          const float a0 = fmaf(acc[i0 + i][j][q], scv[j][k], shv[j][k]);
-          const float a1 = fmaf(acc[i0 + i][j][q + 1], scv[j][k], shv[j][k]);
-          const float got = __builtin_bit_cast(
-              float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, odd ? a0 : a1), 0xb1, 0xf, 0xf, false));
-          float lo = odd ? got : a0, hi = odd ? a1 : got;
-          const int pos = (i * 32 + rr + odd) * WN + j * 32 + cc - odd;
-          if (res) {
-            const uint32_t rp = *reinterpret_cast<const uint32_t*>(res16 + pos);
-            lo += bf16_lo(rp);
-            hi += bf16_lo(rp >> 16);
-          }
-          *reinterpret_cast<uint32_t*>(out16 + pos) = pack_bf16x2(act_apply(lo, d.act), act_apply(hi, d.act));
-        }
-#else
 #pragma unroll
     for (int i = 0; i < NB; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const int rr = L16 ? 16 * (q >> 3) + 4 * (lane >> 4) + (q & 3) : (q & 3) + 8 * (q >> 2) + 4 * h;
-          const int cc = L16 ? 16 * ((q >> 2) & 1) + (lane & 15) : r;
-          const int k = L16 ? (q >> 2) & 1 : 0;
+          const AccPos ap = acc_pos<L16>(q, lane);
+          const int rr = ap.row, cc = ap.col, k = ap.slot;
           const int pos = (i * 32 + rr) * WN + j * 32 + cc;
           float v = fmaf(acc[i0 + i][j][q], scv[j][k], shv[j][k]);
           if (res) v += bf16_lo(res16[pos]);
           out16[pos] = (uint16_t)(pack_bf16x2(act_apply(v, d.act), 0.f) & 0xffffu);
         }
-#endif
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
     __builtin_amdgcn_wave_barrier();
     if (c8) {  // 16-byte pieces (8 channels) where every row piece is aligned and whole
@@ -624,10 +565,9 @@ __device__ __forceinline__ void glds_epilogue(const ConvArgs& p, uint4* smem, in
   const int lane = threadIdx.x & 63;
   const int wm = wave / WN;
   const int wn = wave - wm * WN;
-  const int tilesN = (p.d.Cout + C::BN - 1) / C::BN;
-  const int mt = wg / tilesN;
-  const int n0 = (wg - mt * tilesN) * C::BN;
-  const int64_t m0 = (int64_t)mt * C::BM;
+  const TileOrigin org = tile_origin<C::BM, C::BN>(p, wg);
+  const int64_t m0 = org.m0;
+  const int n0 = org.n0;
   float* smemf = reinterpret_cast<float*>(smem);
   if constexpr (M16) {
     // 16×16 blocks → the f32x16 of their 32×32 block: element q = 8·bi + 4·bj + reg
@@ -663,13 +603,11 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void conv_glds_kernel(const Conv
   // batched launch (Winograd components): member bi owns tiles [bi·tiles_per_batch, (bi+1)·…)
   const int bi = p.batch > 1 ? wg / p.tiles_per_batch : 0;
   wg -= bi * p.tiles_per_batch;
-  const int nk_all = p.K / BK;
-  const int kt0 = (int)(((int64_t)nk_all * blockIdx.z) / p.splits);
-  const int kt1 = (int)(((int64_t)nk_all * (blockIdx.z + 1)) / p.splits);
+  const KRange kr = splitk_range(p, p.K / BK);
   f32x16 acc[TM][TN];
   f32x4 acc4[M16 ? 2 * TM : 1][M16 ? 2 * TN : 1];
   glds_zero<TM, TN, M16>(acc, acc4);
-  glds_main<WM, WN, TM, TN, PL, NS, BK, M16, V, APL>(p, smem, wg, bi, kt0, kt1, acc, acc4);
+  glds_main<WM, WN, TM, TN, PL, NS, BK, M16, V, APL>(p, smem, wg, bi, kr.kt0, kr.kt1, acc, acc4);
   GLDS_STAMP(2);
   __syncthreads();  // every wave done reading the stages before the epilogue reuses the LDS
   ConvArgs q = p;
@@ -705,44 +643,55 @@ int launch_glds_tile(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   constexpr bool fit1a = glds_fit1a<WM, WN, TM, TN, NS, BK, AB>();
   const bool x3 = p.planes == 3, x2 = p.planes == 2, a16 = p.a_bf16, t1 = p.fast_1x1;
   const int epv = p.epilogue;
+  bool launched = false;  // set by the arm that takes the plan; a plan no arm takes is refused below
+#define SP_GLDS_LAUNCH(...)                                                                           \
+  do {                                                                                                \
+    launched = true;                                                                                  \
+    hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, __VA_ARGS__>), grid, blk, 0, s, ab);         \
+  } while (0)
   if constexpr (X2) {  // the split mode's four forms on two planes
     if (x2 && !a16 && t1 && epv == 4)
-      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 2, NS, BK, M16, 2, OCC, 0, 4>), grid, blk, 0, s, ab);
+      SP_GLDS_LAUNCH(2, NS, BK, M16, 2, OCC, 0, 4);
     else if (x2 && !a16 && t1 && epv == 2)
-      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 2, NS, BK, M16, 2, OCC, 0, 2>), grid, blk, 0, s, ab);
+      SP_GLDS_LAUNCH(2, NS, BK, M16, 2, OCC, 0, 2);
     else if (x2 && !a16 && t1)
-      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 2, NS, BK, M16, 2, OCC>), grid, blk, 0, s, ab);
+      SP_GLDS_LAUNCH(2, NS, BK, M16, 2, OCC);
     else if (x2 && !a16)
-      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 2, NS, BK, M16, 1>), grid, blk, 0, s, ab);
+      SP_GLDS_LAUNCH(2, NS, BK, M16, 1);
   } else if (x2) {
     set_error("sp_conv2d: LDS-DMA tile %d is not built for two operand planes", p.tile);
     return -1;
   }
   if constexpr (fit3) {
     if (x3 && !a16 && t1 && epv == 4)
-      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 3, NS, BK, M16, 2, OCC, 0, 4>), grid, blk, 0, s, ab);
+      SP_GLDS_LAUNCH(3, NS, BK, M16, 2, OCC, 0, 4);
     else if (x3 && !a16 && t1 && epv == 2)
-      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 3, NS, BK, M16, 2, OCC, 0, 2>), grid, blk, 0, s, ab);
+      SP_GLDS_LAUNCH(3, NS, BK, M16, 2, OCC, 0, 2);
     else if (x3 && !a16 && t1)
-      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 3, NS, BK, M16, 2, OCC>), grid, blk, 0, s, ab);
+      SP_GLDS_LAUNCH(3, NS, BK, M16, 2, OCC);
     else if (x3 && !a16)
-      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 3, NS, BK, M16, 1>), grid, blk, 0, s, ab);
+      SP_GLDS_LAUNCH(3, NS, BK, M16, 1);
   }
   if constexpr (fit1) {
     if (!x3 && !x2 && !a16 && t1)
-      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 2, OCC>), grid, blk, 0, s, ab);
+      SP_GLDS_LAUNCH(1, NS, BK, M16, 2, OCC);
     else if (!x3 && !x2 && !a16)
-      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 1>), grid, blk, 0, s, ab);
+      SP_GLDS_LAUNCH(1, NS, BK, M16, 1);
   }
   if constexpr (fit1a) {
     if (!x3 && a16 && t1 && epv == 3)
-      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 2, OCC, 1, 3>), grid, blk, 0, s, ab);
+      SP_GLDS_LAUNCH(1, NS, BK, M16, 2, OCC, 1, 3);
     else if (!x3 && a16 && t1)
-      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 2, OCC, 1>), grid, blk, 0, s, ab);
+      SP_GLDS_LAUNCH(1, NS, BK, M16, 2, OCC, 1);
     else if (!x3 && a16 && epv == 3)
-      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 1, 1, 1, 3>), grid, blk, 0, s, ab);
+      SP_GLDS_LAUNCH(1, NS, BK, M16, 1, 1, 1, 3);
     else if (!x3 && a16)
-      hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, 1, NS, BK, M16, 1, 1, 1>), grid, blk, 0, s, ab);
+      SP_GLDS_LAUNCH(1, NS, BK, M16, 1, 1, 1);
+  }
+#undef SP_GLDS_LAUNCH
+  if (!launched) {
+    set_error("sp_conv2d: plan names an instance tile %d is not built with", p.tile);
+    return -1;
   }
   int rc = check_launch(x3 ? "sp_conv2d(f32x3 glds)" : x2 ? "sp_conv2d(f32x2 glds)" : "sp_conv2d(bf16 glds)");
   if (rc || p.splits == 1) return rc;

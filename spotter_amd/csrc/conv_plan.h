@@ -18,10 +18,9 @@
 //   100+id              LDS-DMA                      the same tile with the slab epilogue requested (variant 2,
 //                                                    or 3 on bf16 rows), where its conditions hold
 //   200+id              LDS-DMA                      ... its direct-store form (variant 4) requested
-//   21-26               conv_pipe  (diagnostic)      \
-//   31-32               conv_pp    (diagnostic)       | compiled with -DSP_DIAG_KERNELS=1 only
-//   70-72               conv_x3s   (diagnostic)       | (conv_mfma16.hip); an error in the product library
-//   73-75               conv_x3p   (diagnostic)      /
+//   21-26 31-32 70-75   retired                      the conv_pipe / conv_pp / conv_x3s / conv_x3p kernels, removed
+//                                                    (DESIGN.md "Retired GEMM kernel families"): an error, or
+//                                                    the by-shape rule where plan_conv says so; not reused
 //
 // With bf16 / split operands (planes 1 / 2 / 3) a forced id is read as id, 100+id or 200+id only, so the fp32
 // digit codes mean something else there (220 = 200+20); with fp32 operands only the eighteen digit codes are
@@ -62,8 +61,6 @@ int launch_plan(const ConvArgs& a, const ConvPlan& p, hipStream_t s);
 int launch_fp32(const ConvArgs& a, const ConvPlan& p, hipStream_t s);
 int launch_mfma16(const ConvArgs& a, const ConvPlan& p, hipStream_t s);
 int launch_glds(const ConvArgs& a, const ConvPlan& p, hipStream_t s);
-// conv_mfma16.hip was compiled with -DSP_DIAG_KERNELS=1 (ids 21-26, 31-32, 70-75)
-bool conv_mfma16_has_diag();
 
 // LDS layout of one LDS-DMA tile (conv_glds.h); SMEM (16-byte units) decides which operand modes fit.
 template <int WM, int WN, int TM, int TN, int PL, int NS, int BK, int APL = 0>

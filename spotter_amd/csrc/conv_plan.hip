@@ -241,8 +241,8 @@ int plan_conv(const ConvArgs& a, int planes, const ConvOverrides& o, ConvPlan* p
   int id, req;
   decode_cfg(cfg, &id, &req);
   const GldsTile* t = glds_tile(id);
-  // two planes: an LDS-DMA tile outside kGldsX2Ids, or an id of the diagnostic families (built for one and three
-  // planes), is no id: it falls back by shape, where every tile the rule names is in the set
+  // two planes: an LDS-DMA tile outside kGldsX2Ids, or a retired id (21-32, 70-75: refused below for one and
+  // three planes), is no id: it falls back by shape, where every tile the rule names is in the set
   if (planes == 2 && ((t && !t->a16_only && !t->fit2) || (req == 1 && id >= 21 && id <= 32) ||
                       (req == 1 && id >= 70 && id <= 75))) {
     id = -1;
@@ -283,33 +283,19 @@ int plan_conv(const ConvArgs& a, int planes, const ConvOverrides& o, ConvPlan* p
     return 0;
   }
 
-  const bool a2 = d.A2 != nullptr, diag = conv_mfma16_has_diag();
+  const bool a2 = d.A2 != nullptr;
   const bool reg_id = req == 1 && id >= 0 && id <= 6;  // a register-staged tile (0 runs 4)
   bool by_shape = false;
   if (a2) {
     // only the register-staged tiles take A2: every other forced id (any id >= 11) falls back by shape
     by_shape = !reg_id;
-  } else if (req == 1 && id >= 70 && id <= 75) {
-    if (!diag) {
-      set_error("sp_conv2d: tile configuration %d (conv_x3s / conv_x3p) is in the diagnostic build only", cfg);
-      return -1;
-    }
-    // register epilogues: fp32 rows only; the persistent kernel (73-75) additionally no split-K and the
-    // float4 epilogue. Where they do not hold the id falls back by shape.
-    if (d.C_bf16 || d.res1_bf16 || d.res2_bf16 || (id >= 73 && (a.splits > 1 || !a.vec_epi))) by_shape = true;
-    else {
-      p->family = id >= 73 ? SP_CONV_X3P : SP_CONV_X3S;
-      p->tile = id;
-      return 0;
-    }
-  } else if (req == 1 && ((id >= 21 && id <= 26) || (id >= 31 && id <= 32))) {
-    if (!diag) {
-      set_error("sp_conv2d: tile configuration %d (conv_pipe / conv_pp) is in the diagnostic build only", cfg);
-      return -1;
-    }
-    p->family = id >= 31 ? SP_CONV_PP : SP_CONV_PIPE;
-    p->tile = id;
-    return 0;
+  } else if (req == 1 && ((id >= 21 && id <= 26) || (id >= 31 && id <= 32) || (id >= 70 && id <= 75))) {
+    // retired ids: the conv_pipe / conv_pp / conv_x3s / conv_x3p kernels are gone (DESIGN.md "Retired GEMM
+    // kernel families"). The refusal keeps the words it had while they were a diagnostic build:
+    // tests/golden/conv_plan.jsonl.gz pins the text.
+    set_error("sp_conv2d: tile configuration %d (%s) is in the diagnostic build only", cfg,
+              id >= 70 ? "conv_x3s / conv_x3p" : "conv_pipe / conv_pp");
+    return -1;
   } else if (t && !t->a16_only) {
     // an LDS-DMA tile. (52-56 are honoured with bf16 A rows only: with fp32 A they fall back by shape below.)
   } else if (req > 1 && id >= 11 && id <= 65) {
@@ -384,7 +370,7 @@ int launch_plan(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
     case SP_CONV_FP32:
     case SP_CONV_FUSED_LN: return launch_fp32(a, p, s);
     case SP_CONV_GLDS: return launch_glds(a, p, s);
-    default: return launch_mfma16(a, p, s);  // register-staged, and the diagnostic families
+    default: return launch_mfma16(a, p, s);  // register-staged; it refuses any other family
   }
 }
 

@@ -17,30 +17,6 @@ __device__ __forceinline__ int sw16(int row, int c) { return row * 4 + (c ^ ((ro
 // hi·lo + lo·hi), 6 (the 3-way split).
 constexpr int plane_products(int pl) { return pl == 3 ? 6 : pl == 2 ? 3 : 1; }
 
-// 8 fp32 → PL bf16 planes (RNE). PL = 3: exact residual chain hi / mid / lo; PL = 2: hi and lo = RNE(x - hi)
-// (the residual x - hi - lo, <= 2^-16 |x|, is dropped).
-template <int PL>
-__device__ __forceinline__ void split8(const float4& x0, const float4& x1, bf16x8* out) {
-  static_assert(PL >= 1 && PL <= 3, "operand planes");
-  const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-  bf16x8 h, m, l;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    h[j] = (__bf16)v[j];
-    if constexpr (PL >= 2) {
-      const float r1 = v[j] - (float)h[j];
-      m[j] = (__bf16)r1;
-      if constexpr (PL == 3) {
-        const float r2 = r1 - (float)m[j];
-        l[j] = (__bf16)r2;
-      }
-    }
-  }
-  out[0] = h;
-  if constexpr (PL >= 2) out[1] = m;
-  if constexpr (PL == 3) out[2] = l;
-}
-
 template <int PL>
 __device__ __forceinline__ f32x16 mfma_planes(const bf16x8* a, const bf16x8* b, f32x16 acc) {
   static_assert(PL >= 1 && PL <= 3, "operand planes");
@@ -104,17 +80,14 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
 }
 
-// split8 written pair by pair so it compiles to the minimum VALU stream per 8 elements: 12
-// v_cvt_pk_bf16_f32, 8 + 8 unpacks (the low half of a pair is `u << 16`, the high half `u &
-// 0xffff0000`: bf16 → fp32 is exact) and 16 v_sub_f32 — 44 instructions, against ~60 for the
-// element-wise form (hipcc converts element by element, then repacks). Same RNE hi / mid / lo as split8.
+// 8 fp32 → PL bf16 planes (RNE). PL = 3: exact residual chain hi / mid / lo; PL = 2: hi and lo = RNE(x - hi)
+// (the residual x - hi - lo, <= 2^-16 |x|, is dropped). Written pair by pair so it compiles to the minimum
+// VALU stream per 8 elements: 12 v_cvt_pk_bf16_f32, 8 + 8 unpacks (the low half of a pair is `u << 16`, the
+// high half `u & 0xffff0000`: bf16 → fp32 is exact) and 16 v_sub_f32 — 44 instructions, against ~60 for an
+// element-wise form (hipcc converts element by element, then repacks).
 // PL = 2 stops after the first residual: 8 v_cvt_pk_bf16_f32, 8 unpacks and 8 v_sub_f32 — 24 instructions.
-// Round 5 built the residual subtractions as packed pairs (f32x2 arithmetic → v_pk_add_f32: 36 VALU per 8
-// elements instead of 44, bit-identical); it measured 0.3 % slower in the C2 step (same box, alternating,
-// profiles/r5/x3/ab_round5_changes.json), so the scalar form stays. -DSP_SPLIT_PK2=1: the packed form (A/B).
-#ifndef SP_SPLIT_PK2
-#define SP_SPLIT_PK2 0
-#endif
+// The residual subtractions as packed pairs (v_pk_add_f32: 36 VALU instead of 44, bit-identical) measured
+// 0.3 % slower in the C2 step (profiles/r5/x3/ab_round5_changes.json), so the scalar form stays.
 template <int PL>
 __device__ __forceinline__ void split_frag_pk(const float4& x0, const float4& x1, bf16x8* out) {
   const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
@@ -127,32 +100,16 @@ __device__ __forceinline__ void split_frag_pk(const float4& x0, const float4& x1
     if constexpr (PL == 2) {
       M[q] = cvt_pk_bf16(a - __builtin_bit_cast(float, h << 16), b - __builtin_bit_cast(float, h & 0xffff0000u));
     } else if constexpr (PL == 3) {
-#if SP_SPLIT_PK2
-      const f32x2 ab = {a, b};
-      const f32x2 hf = {__builtin_bit_cast(float, h << 16), __builtin_bit_cast(float, h & 0xffff0000u)};
-      const f32x2 r = ab - hf;
-      const uint32_t m = cvt_pk_bf16(r.x, r.y);
-      M[q] = m;
-      const f32x2 mf = {__builtin_bit_cast(float, m << 16), __builtin_bit_cast(float, m & 0xffff0000u)};
-      const f32x2 r2 = r - mf;
-      L[q] = cvt_pk_bf16(r2.x, r2.y);
-#else
       const float ra = a - __builtin_bit_cast(float, h << 16);
       const float rb = b - __builtin_bit_cast(float, h & 0xffff0000u);
       const uint32_t m = cvt_pk_bf16(ra, rb);
       M[q] = m;
       L[q] = cvt_pk_bf16(ra - __builtin_bit_cast(float, m << 16), rb - __builtin_bit_cast(float, m & 0xffff0000u));
-#endif
     }
   }
   out[0] = __builtin_bit_cast(bf16x8, make_uint4(H[0], H[1], H[2], H[3]));
   if constexpr (PL >= 2) out[1] = __builtin_bit_cast(bf16x8, make_uint4(M[0], M[1], M[2], M[3]));
   if constexpr (PL == 3) out[2] = __builtin_bit_cast(bf16x8, make_uint4(L[0], L[1], L[2], L[3]));
-}
-
-template <int PL>
-__device__ __forceinline__ void split_frag(const float4& x0, const float4& x1, bf16x8* out) {
-  split_frag_pk<PL>(x0, x1, out);
 }
 
 // s_waitcnt vmcnt(n) with expcnt / lgkmcnt left open (gfx9 encoding; n < 64), fenced for the
@@ -200,13 +157,6 @@ __device__ __forceinline__ void glds16s(uint32_t voff, const void* base, uint32_
       : "=&s"(keep)
       : "v"(voff), "s"(sbase), "s"(lds_base)
       : "memory");
-}
-
-// XCD-aware bijective remap of a 1-D grid: MI355X deals consecutive workgroups round-robin over the
-// 8 XCDs, so workgroup b runs on XCD b % 8; index v gives each XCD a contiguous run.
-__device__ __forceinline__ int xcd_index(int b, int nwg) {
-  const int xcd = b & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
 }
 
 }  // namespace

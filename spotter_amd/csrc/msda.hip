@@ -87,10 +87,7 @@ __device__ __forceinline__ float4 corner4(const uint16_t* v) {
 template <typename VT>
 __global__ __launch_bounds__(256) void msda_vec_kernel(const sp_msda_desc d, const VT* __restrict__ value,
                                                        int lanes_per_q) {
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int wg = xcd_index(blockIdx.x, gridDim.x);
   const int qpw = 256 / lanes_per_q;
   const int64_t row = (int64_t)wg * qpw + threadIdx.x / lanes_per_q;  // b*Q + q
   if (row >= (int64_t)d.B * d.Q) return;
@@ -194,10 +191,7 @@ template <typename VT>
 __global__ __launch_bounds__(256) void msda_h8l_kernel(const sp_msda_desc d, const VT* __restrict__ value) {
   constexpr int LPH = 8, LP = 12, P = 4;
   __shared__ __attribute__((aligned(16))) float sh[4 * kH8Wave];
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int wg = xcd_index(blockIdx.x, gridDim.x);
   const int64_t row = (int64_t)wg * 4 + (threadIdx.x >> 6);  // b*Q + q: one query per wave
   if (row >= (int64_t)d.B * d.Q) return;                     // whole waves: no workgroup barrier below
   const int t = threadIdx.x & 63;

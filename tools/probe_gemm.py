@@ -1,7 +1,7 @@
 """Times 1×1 split-GEMM shapes (M rows, Cout, K) over a list of tile configurations, optionally with the
 residual + ReLU epilogue of a bottleneck expand conv — the short-K study of round 2.
 
-    python tools/probe_gemm.py --shapes 51200,1024,256;204800,256,256 --cfgs 44,45,46,73 [--res] [--out f.json]
+    python tools/probe_gemm.py --shapes 51200,1024,256;204800,256,256 --cfgs 44,45,46,63 [--res] [--out f.json]
 """
 from __future__ import annotations
 
@@ -20,7 +20,7 @@ from spotter_amd.ops import view
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", required=True)
-    ap.add_argument("--cfgs", default="-,44,45,46,47,63,65,70,71,72,73,74,75")
+    ap.add_argument("--cfgs", default="-,44,45,46,47,63,65")
     ap.add_argument("--res", action="store_true", help="residual + relu epilogue (res1)")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", default=None)

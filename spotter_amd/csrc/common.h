@@ -64,6 +64,19 @@ __device__ __forceinline__ int xcd_index(int b, int nwg) {
   return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
 }
 
+// Register vectors of the MFMA kernels: operand fragments and accumulators.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// Two fp32 → one packed bf16 pair (RNE): a single v_cvt_pk_bf16_f32.
+__device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
+  const f32x2 v = {a, b};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+}
+
 // A translation unit's bounds log (SP_BOUNDS builds): violations, and the first one's source line, index, extent.
 struct BoundsLog {
   unsigned int hits;

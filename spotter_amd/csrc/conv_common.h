@@ -6,8 +6,6 @@
 
 namespace sp {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 __device__ __forceinline__ float act_apply(float v, int act) {
   if (act == SP_ACT_RELU) return fmaxf(v, 0.0f);
   if (act == SP_ACT_SILU) return v / (1.0f + expf(-v));
@@ -64,6 +62,13 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[TM][TN]) {
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+}
+template <int TM>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[TM]) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[i][q] = 0.f;
 }
 
 // Origin (first row, first column) of BM × BN output tile `wg`, N fastest.

@@ -16,12 +16,13 @@
 // pixels) on v_mfma_f32_32x32x16_bf16. Sums run in (tap, 16-channel step) order with the six products of
 // mfma_planes<3> in its (activation plane, weight plane) sequence lo·hi, hi·lo, mid·mid, mid·hi, hi·mid, hi·hi;
 // the epilogue is epilogue_vec's fmaf(acc, scale, shift) then act, stored as float4 runs.
+#include "direct3x3.h"
 #include "mfma16_common.h"
 
 namespace sp {
 namespace {
 
-constexpr int DX_TH = 8, DX_TW = 32, DX_HR = DX_TH + 2, DX_HC = DX_TW + 2, DX_NPX = DX_HR * DX_HC;
+constexpr int DX_TH = 8, DX_TW = 32, DX_HC = DX_TW + 2;
 
 // RES: all weight stages resident in LDS (loaded once per workgroup) instead of the two-stage ring.
 template <int CIN, int CO, bool RES>
@@ -32,7 +33,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_x3_kernel(const float* __restr
                                                             int64_t ldx, int64_t ldy, int nimg, int h, int w,
                                                             int tiles_x, int tiles_y, int act) {
   constexpr int CPP = CIN / 8;           // 16-byte chunks per pixel per plane
-  constexpr int PLANE = DX_NPX * CPP;    // chunks of one halo plane
+  using Halo = HaloPrefetch<512, DX_TH, DX_TW, CPP, 4, 2>;  // a unit: 8 fp32 in, one chunk of each plane out
+  constexpr int PLANE = Halo::UNITS;     // chunks of one halo plane
   constexpr int SPT = CIN / 32;          // weight stages (32 k each) per tap
   constexpr int NST = 9 * SPT;
   constexpr int WPL = CO * 4;            // chunks of one weight plane of a stage
@@ -40,20 +42,16 @@ __global__ __launch_bounds__(512, 1) void conv3x3_x3_kernel(const float* __restr
   constexpr int NBUF = RES ? NST : 2;
   constexpr int WDMA = WST / 64;         // wave-wide DMAs per stage
   constexpr int TMN = CO / 32;
-  constexpr int PFN = (PLANE + 511) / 512;  // 8-channel halo units per thread
   __shared__ uint4 lds[3 * PLANE + NBUF * WST];
   __shared__ float aff[2 * CO];
+  static_assert(sizeof(lds) + sizeof(aff) == (CIN == 64 ? 155648 : RES ? 120832 : 90368), "static LDS bytes");
   uint4* halo = lds;
   uint4* wl = lds + 3 * PLANE;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  auto hswz = [](int col, int c) { return CIN == 64 ? c ^ ((col >> 1) & 7) : c ^ ((col >> 2) & 3); };
-  if (tid < CO) {
-    aff[tid] = scale[tid];
-    aff[CO + tid] = shift[tid];
-  }
+  stage_affine<CO>(aff, scale, shift);
   // weight stage st (k = 32·st .. +31 of every Cout row, three planes) → ring slot buf: LDS [plane][n][4 chunks],
-  // position q of row n holds global chunk q ^ ((n >> 2) & 3) (the DMA destination is lane-linear)
+  // position q of row n holds global chunk q ^ ((n >> 2) & 3) = swz<4>(n, q) (the DMA destination is lane-linear)
   const uint32_t wl0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint4*)wl;
   auto issue_w = [&](int st, int buf) {
 #pragma unroll
@@ -69,8 +67,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_x3_kernel(const float* __restr
     }
   };
   const int64_t ntiles = (int64_t)nimg * tiles_x * tiles_y;
-  float4 pf[PFN][2];
-  unsigned okm = 0;  // bit k: unit k is inside the map (the others load x[0] and are zeroed at the stash)
+  Halo pf;
+  // Halo::fetch written out: through the shared function this kernel's wait counts change and its Cin-64
+  // instance spills 28 bytes for 24 (profiles/direct_share/README.md)
   auto fetch = [&](int64_t t) {
     const int tx = (int)(t % tiles_x);
     t /= tiles_x;
@@ -79,30 +78,29 @@ __global__ __launch_bounds__(512, 1) void conv3x3_x3_kernel(const float* __restr
     SP_BCHECK(b, nimg);
     const int oy0 = ty * DX_TH, ox0 = tx * DX_TW;
 #pragma unroll
-    for (int k = 0; k < PFN; ++k) {
+    for (int k = 0; k < Halo::PFN; ++k) {
       const int i = tid + k * 512;
       const int c = i % CPP, rc = i / CPP, r = rc / DX_HC, col = rc - r * DX_HC;
       const int iy = oy0 - 1 + r, ix = ox0 - 1 + col;
       const bool ok = i < PLANE && (unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w;
       const int64_t off = ok ? (((int64_t)b * h + iy) * w + ix) * ldx + c * 8 : 0;
       SP_BCHECK(off + 7, ((int64_t)nimg * h * w - 1) * ldx + CIN);
-      pf[k][0] = *reinterpret_cast<const float4*>(x + off);
-      pf[k][1] = *reinterpret_cast<const float4*>(x + off + 4);
-      okm = k == 0 ? (unsigned)ok : (okm | ((unsigned)ok << k));
+      pf.pf[k][0] = *reinterpret_cast<const uint4*>(x + off);
+      pf.pf[k][1] = *reinterpret_cast<const uint4*>(x + off + 4);
+      pf.okm = k == 0 ? (unsigned)ok : (pf.okm | ((unsigned)ok << k));
     }
   };
   // split each fetched unit once (hi / mid / lo, RNE) into the three plane images
   auto stash = [&]() {
 #pragma unroll
-    for (int k = 0; k < PFN; ++k) {
-      const int i = tid + k * 512;
+    for (int k = 0; k < Halo::PFN; ++k) {
+      const int i = Halo::unit(k);
       if (i < PLANE) {
-        const int c = i % CPP, rc = i / CPP, col = rc % DX_HC;
-        const bool ok = (okm >> k) & 1u;
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        const uint4 z = make_uint4(0u, 0u, 0u, 0u);
         bf16x8 pl[3];
-        split_frag_pk<3>(ok ? pf[k][0] : z, ok ? pf[k][1] : z, pl);
-        const int pos = rc * CPP + hswz(col, c);
+        split_frag_pk<3>(__builtin_bit_cast(float4, pf.in_map(k) ? pf.pf[k][0] : z),
+                         __builtin_bit_cast(float4, pf.in_map(k) ? pf.pf[k][1] : z), pl);
+        const int pos = Halo::slot(i);
 #pragma unroll
         for (int q = 0; q < 3; ++q) halo[q * PLANE + pos] = __builtin_bit_cast(uint4, pl[q]);
       }
@@ -121,18 +119,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_x3_kernel(const float* __restr
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     __syncthreads();  // the previous tile's halo reads are done
     stash();
-    int64_t t = tile;
-    const int tx = (int)(t % tiles_x);
-    t /= tiles_x;
-    const int ty = (int)(t % tiles_y);
-    const int b = (int)(t / tiles_y);
-    SP_BCHECK(b, nimg);
-    const int oy = ty * DX_TH + wave, ox = tx * DX_TW + r;
+    const TileAt t = tile_at<DX_TH, DX_TW>(tile, tiles_x, tiles_y, nimg);
+    const int oy = t.oy0 + wave, ox = t.ox0 + r;
     f32x16 acc[TMN];
-#pragma unroll
-    for (int i = 0; i < TMN; ++i)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[i][q] = 0.f;
+    zero_acc(acc);
 #pragma unroll
     for (int st = 0; st < NST; ++st) {
       const int buf = RES ? st : (st + par) & 1;
@@ -151,13 +141,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_x3_kernel(const float* __restr
         const int chw = 2 * s2 + hh;  // k chunk of the stage: channels 32cq + 16s2 + 8hh .. +7
         bf16x8 xa[3], wf[TMN][3];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) xa[q] = *reinterpret_cast<const bf16x8*>(hp + q * PLANE + hswz(col, cq * 4 + chw));
+        for (int q = 0; q < 3; ++q)
+          xa[q] = *reinterpret_cast<const bf16x8*>(hp + q * PLANE + swz<CPP>(col, cq * 4 + chw));
 #pragma unroll
         for (int i = 0; i < TMN; ++i) {
           const int n = i * 32 + r;
 #pragma unroll
           for (int q = 0; q < 3; ++q)
-            wf[i][q] = *reinterpret_cast<const bf16x8*>(wb + q * WPL + n * 4 + (chw ^ ((n >> 2) & 3)));
+            wf[i][q] = *reinterpret_cast<const bf16x8*>(wb + q * WPL + n * 4 + swz<4>(n, chw));
         }
 #pragma unroll
         for (int i = 0; i < TMN; ++i) {
@@ -172,25 +163,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_x3_kernel(const float* __restr
       }
     }
     if constexpr (!RES) par = (par + NST) & 1;
-    // epilogue: lane (pixel r, half hh) holds channels i·32 + 8g + 4hh .. +3 in acc[i][4g .. 4g+3]
     if (oy < h && ox < w) {
-      const int64_t pix = ((int64_t)b * h + oy) * w + ox;
+      const int64_t pix = ((int64_t)t.b * h + oy) * w + ox;
       SP_BCHECK(pix, (int64_t)nimg * h * w);
       float* yrow = y + pix * ldy;
 #pragma unroll
-      for (int i = 0; i < TMN; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int n0 = i * 32 + 8 * g + 4 * hh;
-          float4 v;
-          float* vv = &v.x;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float u = fmaf(acc[i][4 * g + e], aff[n0 + e], aff[CO + n0 + e]);
-            vv[e] = act ? fmaxf(u, 0.f) : u;
-          }
-          *reinterpret_cast<float4*>(yrow + n0) = v;
-        }
+      for (int i = 0; i < TMN; ++i) epilogue_f32<CO>(acc[i], i * 32, hh, aff, yrow, act);
     }
   }  // tiles
   wait_vmcnt<0>();  // the ring's last DMA (issued for a tile that does not come) lands before the LDS is released
@@ -199,11 +177,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_x3_kernel(const float* __restr
 template <int CIN, int CO, bool RES>
 int dx_launch(const char* what, const float* x, int64_t ldx, const uint16_t* wp, int64_t wps, const float* scale,
               const float* shift, float* y, int64_t ldy, int n, int h, int w, int act, void* stream) {
-  const int tiles_x = (w + DX_TW - 1) / DX_TW, tiles_y = (h + DX_TH - 1) / DX_TH;
-  const int64_t tiles = (int64_t)n * tiles_x * tiles_y;
-  const unsigned grid = (unsigned)(tiles < g_num_cus ? tiles : g_num_cus);  // persistent: one per CU
-  hipLaunchKernelGGL((conv3x3_x3_kernel<CIN, CO, RES>), dim3(grid), dim3(512), 0, as_stream(stream), x, wp, wps,
-                     scale, shift, y, ldx, ldy, n, h, w, tiles_x, tiles_y, act);
+  const DirectGrid g = direct_grid<DX_TH, DX_TW>(n, h, w, g_num_cus);  // persistent: one per CU
+  hipLaunchKernelGGL((conv3x3_x3_kernel<CIN, CO, RES>), dim3(g.grid), dim3(512), 0, as_stream(stream), x, wp, wps,
+                     scale, shift, y, ldx, ldy, n, h, w, g.tiles_x, g.tiles_y, act);
   return check_launch(what);
 }
 

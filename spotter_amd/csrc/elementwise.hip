@@ -105,14 +105,9 @@ __device__ __forceinline__ void unpack8(const uint4 u, float* f) {
     f[2 * i + 1] = __builtin_bit_cast(float, w[i] & 0xffff0000u);
   }
 }
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  const f2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, b2));
-}
 __device__ __forceinline__ uint4 pack8(const float* f) {
-  return make_uint4(pk_bf16(f[0], f[1]), pk_bf16(f[2], f[3]), pk_bf16(f[4], f[5]), pk_bf16(f[6], f[7]));
+  return make_uint4(cvt_pk_bf16(f[0], f[1]), cvt_pk_bf16(f[2], f[3]), cvt_pk_bf16(f[4], f[5]),
+                    cvt_pk_bf16(f[6], f[7]));
 }
 
 __global__ __launch_bounds__(256) void maxpool3s2_bf16_kernel(const uint4* __restrict__ x, uint4* __restrict__ y,
@@ -353,7 +348,7 @@ __global__ __launch_bounds__(256) void layernorm256_kernel(const float* __restri
     const float4 o = make_float4((v[i].x - mean) * rstd * gg[i].x + bb[i].x, (v[i].y - mean) * rstd * gg[i].y + bb[i].y,
                                  (v[i].z - mean) * rstd * gg[i].z + bb[i].z, (v[i].w - mean) * rstd * gg[i].w + bb[i].w);
     if (y16)
-      reinterpret_cast<uint2*>(y16 + row * ldy)[l16 + 16 * i] = make_uint2(pk_bf16(o.x, o.y), pk_bf16(o.z, o.w));
+      reinterpret_cast<uint2*>(y16 + row * ldy)[l16 + 16 * i] = make_uint2(cvt_pk_bf16(o.x, o.y), cvt_pk_bf16(o.z, o.w));
     else
       reinterpret_cast<float4*>(y + row * ldy)[l16 + 16 * i] = o;
   }

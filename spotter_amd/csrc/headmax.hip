@@ -17,9 +17,6 @@
 namespace sp {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int HM_NP = 96;     // class columns staged (3 blocks of 32)
 
 template <int KC>  // K / 8: 16-byte chunks per row

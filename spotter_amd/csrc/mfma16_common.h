@@ -7,8 +7,6 @@
 namespace sp {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int KT = 32;  // k per LDS stage
 
 __device__ __forceinline__ int sw16(int row, int c) { return row * 4 + (c ^ ((row >> 2) & 3)); }
@@ -35,8 +33,6 @@ __device__ __forceinline__ f32x16 mfma_planes(const bf16x8* a, const bf16x8* b, 
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
   }
 }
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Same six-product sum on v_mfma_f32_16x16x32_bf16 (one 16×16 block, k = 32 per instruction).
 template <int PL>
@@ -70,15 +66,6 @@ __device__ __forceinline__ f32x4 mfma16x16_planes(const bf16x8* a, const bf16x8*
 // the fp32 kernel's swizzle), position q of a B row holds chunk q ^ ((r >> 2) & 3) (sw16).
 // Padding taps, rows past M and columns past Cout read a 128-byte zero block instead.
 __device__ float4 g_zero_chunk[16];  // 256 B: the widest staged row chunk offset (fp32 A at BK = 64) stays inside
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// Two fp32 → one packed bf16 pair (RNE): a single v_cvt_pk_bf16_f32.
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
 
 // 8 fp32 → PL bf16 planes (RNE). PL = 3: exact residual chain hi / mid / lo; PL = 2: hi and lo = RNE(x - hi)
 // (the residual x - hi - lo, <= 2^-16 |x|, is dropped). Written pair by pair so it compiles to the minimum

@@ -332,10 +332,14 @@ def test_launcher_constants_match_the_sources():
     """The tile sizes, caps and gates above are read from the launchers: hold them to the source text."""
     src = lambda f: open(os.path.join(cr.ROOT, "spotter_amd", "csrc", f)).read()
     stem, x3, el, pre = src("stem.hip"), src("direct_x3.hip"), src("elementwise.hip"), src("preprocess.hip")
-    assert "constexpr int C3_TW = 64;" in stem and "constexpr int RPW = 1;" in stem and "TH = 4 * RPW" in stem
+    shared = src("direct3x3.h")
+    assert "constexpr int C3_TW = 64;" in stem and "constexpr int C3_TH = 4;" in stem
     assert "constexpr int F3_TH = 8," in stem and "constexpr int B6_TH = 16, B6_TW = 32," in stem
     assert "g_num_cus * (cout == 32 ? 3 : 2)" in stem and "constexpr int STEM_BLOCK = 256;" in stem
-    assert "constexpr int DX_TH = 8, DX_TW = 32," in x3 and "tiles < g_num_cus ? tiles : g_num_cus" in x3
+    assert "direct_grid<C3_TH, C3_TW>(n, h, w, cap)" in stem and "direct_grid<F3_TH, C3_TW>(n, h, w, g_num_cus)" in stem
+    assert "direct_grid<B6_TH, B6_TW>(n, h, w, g_num_cus)" in stem
+    assert "constexpr int DX_TH = 8, DX_TW = 32," in x3 and "direct_grid<DX_TH, DX_TW>(n, h, w, g_num_cus)" in x3
+    assert "tiles_x = (w + TW - 1) / TW, tiles_y = (h + TH - 1) / TH;" in shared and "tiles < cap ? tiles : cap" in shared
     assert "constexpr int MP_ROWS = 4;" in el and ">= 16384 ? MP_ROWS : 1" in el and "if (g > 256 * 16) g = 256 * 16;" in el
     assert "constexpr int kMaxImgs = 32;" in pre and "constexpr int kLdsBytes = 48 * 1024;" in pre
     assert "constexpr int kColTile = 256;" in pre

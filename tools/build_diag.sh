@@ -2,7 +2,7 @@
 # Diagnostic library builds into spotter_amd/_diag/ (not the product): tools/build_diag.sh <name> <-D flags...>
 # e.g. tools/build_diag.sh stamp -DSP_GLDS_STAMP=1 → spotter_amd/_diag/libspotter_stamp.so (conv_glds.hip rebuilt
 # with the flags, every other object from spotter_amd/_build/). Use with SPOTTER_HIP_LIB=<that .so>.
-# UNIT=stem rebuilds csrc/stem.hip instead (e.g. UNIT=stem tools/build_diag.sh c64abl1 -DSP_C64_ABL=1).
+# UNIT=<unit> rebuilds csrc/<unit>.hip instead (e.g. UNIT=stem tools/build_diag.sh stemdiag -DSP_BOUNDS=0).
 set -e
 cd "$(dirname "$0")/.."
 NAME=$1; shift

@@ -184,6 +184,8 @@ int sp_set_splitk_config(int cfg, int max_splits, int min_ktiles);
 enum sp_tuning_knob {
   SP_TUNE_GLDS_EPILOGUE = 3,  /* split-mode slab epilogue: 4 = outputs stored from the accumulators, else the slab pass */
   SP_TUNE_MSDA_GENERIC = 4,   /* ABI v14: 1 = sp_msda's per-lane kernel where the point-sharing one applies (A/B) */
+  SP_TUNE_FOLD = 5,           /* the folded split-K tile (sp_set_plan_batch): 1 = never (the split launch + reduce), 2 = for every
+                               * split-K launch of the register-staged 64x64 tile (tests, A/B; bit-identical either way) */
 };
 int sp_set_tuning(int knob, int value);
 /* ABI v18: the kernel instantiation sp_conv2d would launch for this descriptor under the calling thread's
@@ -209,6 +211,40 @@ typedef struct {
   int32_t counters;  /* 1: split-K combined in the launch (arrival counters), 0: the reduce launch */
 } sp_conv_plan_info;
 int sp_conv_plan(const sp_conv_desc* d, sp_conv_plan_info* out);
+/* Batch-invariant planning (additive to ABI v20; a PRODUCT-PATH call, unlike the sp_set_* hooks above, and like them
+ * per calling thread and never read from the environment). While set with batch >= 1 and plan_batch >= 1, a launch
+ * whose rows are `batch` images is planned as the launch of `plan_batch` images would be: sp_conv2d, sp_conv_plan, the
+ * Winograd stages, sp_conv3x3_winograd and sp_winograd_plan choose the kernel family, the tile, the operand form and
+ * the split-K factor for M' = M * plan_batch / batch rows (M: the launch's rows, N*Ho*Wo, or the Winograd tile count
+ * T) and run that choice on the M rows given. sp_set_plan_batch(0, 0), the initial state, plans from M. Returns 0,
+ * or < 0 for any other argument below 1.
+ *
+ * THE INVARIANT: a row's output bits depend only on the row's operands, the descriptor's per-image fields and
+ * plan_batch, never on batch (nor on which slot of the batch the image takes).
+ *
+ * While it is set (batch >= 1, whether or not batch == plan_batch):
+ *  - M % batch != 0 is an argument error;
+ *  - the split-K factor is the one M' rows give with this descriptor's workspace_elems; a workspace too short for
+ *    that factor on the M rows of the launch (splits * M * ldp elements) is an argument error, never a smaller
+ *    factor. Callers size the workspace for splits * M;
+ *  - the 1x1 fast path's 32-bit addressing limit (M * lda * 4 < 2^32) is the launch's own: see fast_1x1 below.
+ * The plan queries answer under the same setting from the same functions the launches run (the rule of v18 / v20).
+ *
+ * sp_conv_plan_info under the setting. family, tile, planes, generic, a_bf16 and splits follow M' (generic and
+ * a_bf16 never depended on M). The others are addressing or resource limits of the launch at hand and keep
+ * following M; their alternatives are bit-identical:
+ *  - counters (needs splitk_counters_len >= the launch's tiles and slabs below 2^31 bytes): the in-launch combine
+ *    sums the slabs in z order with splitk_reduce_kernel's arithmetic
+ *    (tests/test_gpu_kernels.py::test_splitk_in_launch_combine_bit_identical);
+ *  - epilogue (variant 4 needs the output rows below 2^31 bytes): only variant 4 against variant 2 depends
+ *    on M, and the two store the same values (tests/test_gpu_kernels.py::test_direct_store_epilogue_bit_identical);
+ *  - fast_1x1 (needs M * lda * 4 < 2^32): the same MFMA sequence on the same operands, only the address arithmetic
+ *    differs (tests/test_gpu_batch_invariant.py::test_fast_1x1_is_bit_identical).
+ * Where a split is planned for M' and a grid of M rows would not split, the register-staged 64x64 tile runs it
+ * folded: one workgroup per tile walks the k-ranges in turn and adds the partial tiles in z order in registers,
+ * bit-identical to the split launch + reduce (tests/test_gpu_batch_invariant.py::test_folded_matches_split_reduce);
+ * the plan reports the same splits either way. */
+int sp_set_plan_batch(int batch, int plan_batch);
 
 /* 3x3 stride-1 pad-1 convolution by Winograd F(2x2, 3x3) (ABI v9): the same result contract as
  * sp_conv2d on the same descriptor (KH = KW = 3, stride 1, pad 1; act, scale / shift, res1 / res2 as

@@ -138,6 +138,7 @@ _SIGS = {
     "sp_set_conv_config": (i32, [i32]),
     "sp_set_splitk_config": (i32, [i32, i32, i32]),
     "sp_set_tuning": (i32, [i32, i32]),
+    "sp_set_plan_batch": (i32, [i32, i32]),
     "sp_conv_plan": (i32, [C.POINTER(SpConvDesc), C.POINTER(SpConvPlanInfo)]),
     "sp_winograd_plan": (i32, [C.POINTER(SpConvDesc), i32, i64, i64, C.POINTER(SpWinogradPlanInfo)]),
     "sp_conv3x3_winograd": (i32, [C.POINTER(SpConvDesc), vp, i64, vp, i64, vp]),

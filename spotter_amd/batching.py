@@ -8,7 +8,9 @@ into one engine forward: a single collector thread owns the device engine, takes
 `max_batch` queued images of the same shape within `max_wait_ms` of the first, runs them as
 one batch and hands each caller its own rows. Images never interact in the forward (every
 kernel is per image / per query), so a caller gets what its own bs1 call computes up to fp32
-summation order (bs1 GEMMs use split-K).
+summation order (bs1 GEMMs use split-K). With the model's batch_invariant=P (Engine) it gets the same
+bits as its own call at any batch: the batcher needs nothing of its own for that, since it only runs `run_batch` (the
+model's `_run`, which plans every forward as P images) and hands out rows.
 """
 from __future__ import annotations
 

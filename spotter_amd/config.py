@@ -133,3 +133,30 @@ def check_precision(precision: str) -> str:
     if precision not in PRECISIONS:
         raise ValueError(f"precision {precision!r} (e.g. from {PRECISION_ENV}) must be one of {sorted(PRECISIONS)}")
     return precision
+
+
+BATCH_INVARIANT_ENV = "SPOTTER_BATCH_INVARIANT"
+
+
+def check_batch_invariant(value):
+    """None (off), or the plan batch P of the batch-invariant mode as an int >= 1 (engine.Engine documents the mode);
+    else ValueError naming the env variable that may have set it. bool is refused: True is no batch size."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+        raise ValueError(f"batch_invariant {value!r} (e.g. from {BATCH_INVARIANT_ENV}) must be None or an int >= 1")
+    return int(value)
+
+
+def batch_invariant_from_env(environ=None):
+    """SPOTTER_BATCH_INVARIANT: unset, empty, "0" or "off" = None; a decimal integer >= 1 = the plan batch; anything
+    else raises ValueError (at import of the drop-in serve.py, like a bad SPOTTER_PRECISION)."""
+    import os
+
+    raw = (os.environ if environ is None else environ).get(BATCH_INVARIANT_ENV)
+    if raw is None or raw.strip().lower() in ("", "0", "off"):
+        return None
+    txt = raw.strip()
+    if not (txt.isascii() and txt.isdigit()):
+        raise ValueError(f"{BATCH_INVARIANT_ENV}={raw!r} must be off, 0 or an integer >= 1")
+    return check_batch_invariant(int(txt))

@@ -37,6 +37,12 @@ struct ConvArgs {
   // launchers whose kernels call splitk_combine, from sp_conv_desc.splitk_counters, where the plan says so);
   // null: the reduce launch
   int32_t* counters = nullptr;
+  // The row count every size-dependent choice is made from (plan_conv, the Winograd tile rule): M, or under
+  // sp_set_plan_batch(batch, plan_batch) M · plan_batch / batch. Host-side only: no kernel reads it.
+  int64_t Mp = 0;
+  // Folded split-K (conv_mfma16.hip): the plan's `splits` k-ranges walked in turn by one workgroup per output
+  // tile, combined in registers in z order. Set where the plan splits for Mp rows but a grid of M rows would not.
+  int32_t fold = 0;
 };
 
 // ---- Pieces the GEMM kernels share (conv_gemm.hip, conv_mfma16.hip, conv_glds.h).

@@ -41,7 +41,13 @@ namespace {
 
 // CNT: a split-K instance, which may combine in the launch (splitk_combine); other instances keep the plain
 // epilogue.
-template <int WM, int WN, int TM, int TN, int PL, bool FAST, bool CNT = false>
+// FOLD: folded split-K (ConvArgs::fold = S > 1, splits = 1, grid z = 1). The workgroup walks the S k-ranges a
+// split launch would give its S workgroups (the same boundaries, nk·z / S), each into a freshly zeroed accumulator,
+// and adds the partial tiles in z order — tot = acc₀, tot += acc_z: splitk_reduce_kernel's sum, element by element,
+// on the registers that hold the element (no cross-lane exchange, no workspace) — then runs the epilogue once.
+// Bit-identical to the split launch + reduce. Registers: the 64×64 tile's wave holds one f32x16 accumulator, so the
+// running sum costs 16 VGPRs more.
+template <int WM, int WN, int TM, int TN, int PL, bool FAST, bool CNT = false, bool FOLD = false>
 __global__ __launch_bounds__(64 * WM * WN) void conv_mfma16_kernel(const ConvArgs p) {
   constexpr int NT = 64 * WM * WN;
   constexpr int BM = 32 * TM * WM;
@@ -220,20 +226,45 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma16_kernel(const ConvArg
     }
   };
 
-  const KRange kr = splitk_range(p, (p.K + KT - 1) / KT);
-  const int kt0 = kr.kt0;
-  const int nk = kr.kt1 - kt0;
-  if constexpr (FAST) walk.seek(d, kt0 * KT);
-  if (nk > 0) {
-    load_tile(kt0);
-    store_tile(smem);
-  }
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    if (kt + 1 < nk) load_tile(kt0 + kt + 1);
-    compute_tile(smem + (kt & 1) * STAGE);
-    if (kt + 1 < nk) store_tile(smem + ((kt + 1) & 1) * STAGE);
+  // one k-range [kt0, kt0 + nk) into acc; every wave has passed the last barrier when it returns, so the next
+  // range may overwrite stage 0
+  auto run_range = [&](int kt0, int nk) {
+    if constexpr (FAST) walk.seek(d, kt0 * KT);
+    if (nk > 0) {
+      load_tile(kt0);
+      store_tile(smem);
+    }
     __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+      if (kt + 1 < nk) load_tile(kt0 + kt + 1);
+      compute_tile(smem + (kt & 1) * STAGE);
+      if (kt + 1 < nk) store_tile(smem + ((kt + 1) & 1) * STAGE);
+      __syncthreads();
+    }
+  };
+  const int nk_all = (p.K + KT - 1) / KT;
+  if constexpr (FOLD) {
+    f32x16 tot[TM][TN];
+    const int S = p.fold;
+    for (int z = 0; z < S; ++z) {
+      const int kt0 = (int)(((int64_t)nk_all * z) / S);
+      const int kt1 = (int)(((int64_t)nk_all * (z + 1)) / S);
+      if (z) zero_acc(acc);
+      run_range(kt0, kt1 - kt0);
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int q = 0; q < 16; ++q) tot[i][j][q] = z ? tot[i][j][q] + acc[i][j][q] : acc[i][j][q];
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) acc[i][j] = tot[i][j];
+  } else {
+    const KRange kr = splitk_range(p, nk_all);
+    run_range(kr.kt0, kr.kt1 - kr.kt0);
   }
 
   float* smemf = reinterpret_cast<float*>(smem);
@@ -252,6 +283,21 @@ int launch_cfg(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   dim3 grid((unsigned)tiles, 1, p.splits);
   ConvArgs b = a;
   b.counters = p.counters ? a.d.splitk_counters : nullptr;
+  if constexpr (WM == 2 && WN == 2 && TM == 1 && TN == 1) {
+    if (a.fold && p.splits > 1) {  // the folded 64×64 split tile: one launch, no partial slabs, no reduce
+      b.fold = p.splits;
+      b.splits = 1;
+      b.counters = nullptr;
+      grid.z = 1;
+      if (p.planes == 3)
+        hipLaunchKernelGGL((conv_mfma16_kernel<2, 2, 1, 1, 3, true, false, true>), grid, dim3(256), 0, s, b);
+      else if (p.planes == 2)
+        hipLaunchKernelGGL((conv_mfma16_kernel<2, 2, 1, 1, 2, true, false, true>), grid, dim3(256), 0, s, b);
+      else
+        hipLaunchKernelGGL((conv_mfma16_kernel<2, 2, 1, 1, 1, true, false, true>), grid, dim3(256), 0, s, b);
+      return check_launch("sp_conv2d(folded split-K)");
+    }
+  }
   if (p.counters && p.planes == 3)
     hipLaunchKernelGGL((conv_mfma16_kernel<WM, WN, TM, TN, 3, true, true>), grid, dim3(64 * WM * WN), 0, s, b);
   else if (p.counters && p.planes == 2)

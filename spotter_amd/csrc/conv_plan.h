@@ -46,6 +46,18 @@ struct ConvOverrides {
 };
 const ConvOverrides& conv_overrides();
 
+// sp_set_plan_batch (spotter_hip.h) of the calling thread: while batch > 0, launches of `batch` images are planned
+// as launches of `plan` images. fold (sp_set_tuning SP_TUNE_FOLD, tests and A/B only): 0 = the rule (conv_args),
+// 1 = never the folded split-K form, 2 = every split that the register-staged 64×64 tile runs.
+struct PlanBatch {
+  int batch = 0, plan = 0, fold = 0;
+};
+const PlanBatch& plan_batch();
+// The rows a launch of `rows` rows is planned as: rows, or rows · plan / batch under sp_set_plan_batch (rows that
+// are no multiple of the batch: -1 with the error set). The one place every size-dependent choice of the conv /
+// linear planner and of the Winograd stages takes its row count from.
+int plan_rows(const char* what, int64_t rows, int64_t* out);
+
 // sp_conv2d's argument checks and the derived launch arguments (M, K, fast, vec_epi, split-K factor):
 // 0, or -1 with the error set. `planes`: 0 fp32, 1 bf16, 2 the 2-way split, 3 the 3-way split.
 int conv_args(const sp_conv_desc* d, const ConvOverrides& o, ConvArgs* a, int* planes);

@@ -16,11 +16,29 @@ constexpr int BK = 32;
 #endif
 
 thread_local ConvOverrides g_overrides;
+thread_local PlanBatch g_plan_batch;
 
 // BM × BN of the register-staged tiles 1-6 (conv_mfma16.hip launch_mfma16); 0 runs 4
 constexpr int kRegTile[7][2] = {{64, 64}, {128, 128}, {256, 128}, {64, 128}, {64, 64}, {128, 256}, {128, 64}};
 
+// tiles of the grid the launch runs (M rows: the grid limit, the counters' length) ...
 int64_t tiles_of(const ConvArgs& a, int bm, int bn) { return ((a.M + bm - 1) / bm) * ((a.d.Cout + bn - 1) / bn); }
+// ... and of the rows the choice is made for (Mp: every fill threshold of the by-shape rules)
+int64_t plan_tiles_of(const ConvArgs& a, int bm, int bn) { return ((a.Mp + bm - 1) / bm) * ((a.d.Cout + bn - 1) / bn); }
+
+// The split-K factor a GEMM of `rows` rows asks for, before the descriptor's conditions and the cap
+// (measured at bs1, profiles/r1/bs1_detail_*.json): short grids split to ~512 workgroups with >= 8 k-tiles
+// each; tiny-M linears (< 64 tiles) split even at K = 256; grids of up to SP_SPLITK_BLOCKS tiles split only
+// when each workgroup would walk >= 64 k-tiles.
+int split_for(int64_t rows, int cout, int nk, const ConvOverrides& o) {
+  const int64_t blocks64 = ((rows + 63) / 64) * ((cout + 63) / 64);
+  int sp = 1;
+  if (nk < o.splitk_min_nk) sp = 1;
+  else if (blocks64 < 64 && nk >= 8 && nk < 16) sp = nk / 4;
+  else if (blocks64 < 256 && nk >= 16) sp = (int)((512 + blocks64 - 1) / blocks64), sp = sp < nk / 8 ? sp : nk / 8;
+  else if (blocks64 < SP_SPLITK_BLOCKS && nk >= 64) sp = (int)((SP_SPLITK_BLOCKS + blocks64 - 1) / blocks64);
+  return sp;
+}
 
 // A split-K launch of `tiles` output tiles combines in the launch: the descriptor's counter array has one
 // entry per tile, and the partial slabs are addressable by 32-bit buffer offsets (at most 16 splits); else the
@@ -89,6 +107,17 @@ int plan_glds_tile(const ConvArgs& a, int planes, const GldsTile& t, int req, Co
 }  // namespace
 
 const ConvOverrides& conv_overrides() { return g_overrides; }
+const PlanBatch& plan_batch() { return g_plan_batch; }
+
+int plan_rows(const char* what, int64_t rows, int64_t* out) {
+  const PlanBatch& b = g_plan_batch;
+  *out = rows;
+  if (b.batch <= 0) return 0;
+  SP_ARG_CHECK(rows % b.batch == 0, "%s: %lld rows are no multiple of the batch %d of sp_set_plan_batch", what,
+               (long long)rows, b.batch);
+  *out = rows / b.batch * b.plan;
+  return 0;
+}
 
 int conv_args(const sp_conv_desc* d, const ConvOverrides& o, ConvArgs* out, int* out_planes) {
   SP_ARG_CHECK(d != nullptr, "sp_conv2d: null descriptor");
@@ -130,6 +159,7 @@ int conv_args(const sp_conv_desc* d, const ConvOverrides& o, ConvArgs* out, int*
   a.d = *d;
   a.A16 = d->A_bf16;
   a.M = (int64_t)d->N * ho * wo;
+  if (plan_rows("sp_conv2d", a.M, &a.Mp)) return -1;
   a.K = (int32_t)K;
   a.HoWo = ho * wo;
   // fast operand path: every 32-deep k-tile lies in one filter tap, and the rows loaded as
@@ -157,21 +187,23 @@ int conv_args(const sp_conv_desc* d, const ConvOverrides& o, ConvArgs* out, int*
   a.ldp = (d->Cout + 3) & ~3;
   a.partial = d->workspace;
   {
-    const int64_t blocks64 = ((a.M + 63) / 64) * ((d->Cout + 63) / 64);
     const int nk = (a.K + BK - 1) / BK;
-    // measured at bs1 (profiles/r1/bs1_detail_*.json): short grids split to ~512 workgroups with
-    // ≥ 8 k-tiles each; tiny-M linears (< 64 tiles) split even at K = 256; grids of up to
-    // SP_SPLITK_BLOCKS tiles split only when each workgroup would walk ≥ 64 k-tiles.
-    int sp = 1;
-    if (nk < o.splitk_min_nk) sp = 1;
-    else if (blocks64 < 64 && nk >= 8 && nk < 16) sp = nk / 4;
-    else if (blocks64 < 256 && nk >= 16) sp = (int)((512 + blocks64 - 1) / blocks64), sp = sp < nk / 8 ? sp : nk / 8;
-    else if (blocks64 < SP_SPLITK_BLOCKS && nk >= 64) sp = (int)((SP_SPLITK_BLOCKS + blocks64 - 1) / blocks64);
+    int sp = split_for(a.Mp, d->Cout, nk, o);
     // split-K runs on the register-staged tiles (fp32 A) and reduces through the fp32-row epilogue
     if (d->workspace && sp > 1 && !d->A_bf16 && !d->C_bf16 && !d->res1_bf16 && !d->res2_bf16) {
       if (sp > o.splitk_max) sp = o.splitk_max;
-      while (sp > 1 && (int64_t)sp * a.M * a.ldp > d->workspace_elems) --sp;
+      // a workspace too short for sp slabs of the planned rows lowers the factor ...
+      while (sp > 1 && (int64_t)sp * a.Mp * a.ldp > d->workspace_elems) --sp;
+      // ... but under sp_set_plan_batch never one too short for the rows of this launch: that would make the
+      // factor, and with it the order of the sum, depend on the batch
+      SP_ARG_CHECK(g_plan_batch.batch <= 0 || sp == 1 || (int64_t)sp * a.M * a.ldp <= d->workspace_elems,
+                   "sp_conv2d: workspace %lld < %lld elements (the %d-way split-K planned for %lld rows, on %lld rows; "
+                   "sp_set_plan_batch does not lower the factor)", (long long)d->workspace_elems,
+                   (long long)((int64_t)sp * a.M * a.ldp), sp, (long long)a.Mp, (long long)a.M);
       if (sp > 1) a.splits = sp;
+      // planned for fewer rows than the launch has, on a grid that would not split: the folded form
+      a.fold = sp > 1 && g_plan_batch.fold != 1 &&
+               (g_plan_batch.fold == 2 || (a.Mp != a.M && split_for(a.M, d->Cout, nk, o) == 1));
     }
   }
   if (d->ln_gamma) {  // Linear → +residual → LayerNorm in one launch: 32-row tiles holding whole rows
@@ -180,6 +212,7 @@ int conv_args(const sp_conv_desc* d, const ConvOverrides& o, ConvArgs* out, int*
                  "sp_conv2d: fused LayerNorm needs fp32 weights, Cout %% 128 == 0 <= 512, no act / res2 / "
                  "grouped rows, Cin %% 32 == 0 (Cout=%d)", d->Cout);
     a.splits = 1;
+    a.fold = 0;
   }
   *out_planes = planes;
   return 0;
@@ -187,7 +220,8 @@ int conv_args(const sp_conv_desc* d, const ConvOverrides& o, ConvArgs* out, int*
 
 int plan_conv(const ConvArgs& a, int planes, const ConvOverrides& o, ConvPlan* p) {
   const sp_conv_desc& d = a.d;
-  const auto tiles = [&](int bm, int bn) { return tiles_of(a, bm, bn); };
+  // the fill thresholds below count the tiles of the planned rows (Mp); grid limits count the launch's own
+  const auto tiles = [&](int bm, int bn) { return plan_tiles_of(a, bm, bn); };
   *p = ConvPlan{};
   p->planes = planes;
   p->epilogue = 1;
@@ -206,7 +240,7 @@ int plan_conv(const ConvArgs& a, int planes, const ConvOverrides& o, ConvPlan* p
   // for the same descriptor (the table key, the by-shape rule, the slab epilogue), sp: "split operands".
   const bool sp = planes >= 2;
   int cfg = o.cfg;
-  if (cfg < 0 && a.splits == 1) cfg = tile_table_lookup(a.M, d.Cout, a.K, d.KH, d.stride, sp ? 3 : planes);
+  if (cfg < 0 && a.splits == 1) cfg = tile_table_lookup(a.Mp, d.Cout, a.K, d.KH, d.stride, sp ? 3 : planes);
   if (cfg < 0 && a.splits > 1 && planes && o.splitk_cfg >= 0) cfg = o.splitk_cfg;
 
   if (planes == 0) {  // ---- fp32 MFMA
@@ -214,7 +248,7 @@ int plan_conv(const ConvArgs& a, int planes, const ConvOverrides& o, ConvPlan* p
     p->generic = !a.fast;
     if (a.splits > 1) {  // split-K runs the 64×64 tile whatever id is forced; combined in the launch with counters
       p->tile = 110;
-      p->counters = counters_ok(a, tiles(64, 64));
+      p->counters = counters_ok(a, tiles_of(a, 64, 64));
       return 0;
     }
     switch (cfg) {
@@ -230,8 +264,8 @@ int plan_conv(const ConvArgs& a, int planes, const ConvOverrides& o, ConvPlan* p
     // Cout <= 32 (stem): the 4×1 wave grid's 128×32 tile, no idle N half (1.69× on the stem 3×3,
     // 1.23× on the Cin = 3 stem conv; profiles/r1/conv_bench_thin_fp32.jsonl).
     if (d.Cout <= 32) p->tile = 4110;
-    else if (d.Cout <= 64 && a.M >= 500000 && a.K >= 288) p->tile = 210;
-    else if (a.K >= 3000 && d.Cout >= 384 && a.M >= 100000) p->tile = 220;
+    else if (d.Cout <= 64 && a.Mp >= 500000 && a.K >= 288) p->tile = 210;
+    else if (a.K >= 3000 && d.Cout >= 384 && a.Mp >= 100000) p->tile = 220;
     else if (a.K <= 128 || d.Cout <= 64 || tiles(64, 64) < 3000) p->tile = 110;
     else p->tile = 120;
     return 0;
@@ -320,12 +354,12 @@ int plan_conv(const ConvArgs& a, int planes, const ConvOverrides& o, ConvPlan* p
     const bool x3 = sp;
     if (a.splits > 1) id = 4;
     else if (dma && x3 && a.K <= 256 && d.Cout >= 512 && tiles(128, 128) >= 192) id = 46;
-    else if (dma && x3 && d.Cout % 128 == 0 && d.Cout % 256 != 0 && a.M >= 40000 &&
-             (a.M < 150000 || d.Cout == 128) && tiles(128, 128) >= 192) id = 45;
+    else if (dma && x3 && d.Cout % 128 == 0 && d.Cout % 256 != 0 && a.Mp >= 40000 &&
+             (a.Mp < 150000 || d.Cout == 128) && tiles(128, 128) >= 192) id = 45;
     else if (d.Cout <= 64)
       id = dma ? (x3 && d.Cout == 64 && tiles(256, 64) >= 192 ? 51 : (tiles(128, 64) >= 192 ? 16 : 14)) : 4;
     else if (dma && d.Cout % 256 == 0 && a.K >= 512 && tiles(256, 256) >= 192) id = 33;
-    else if (tiles(256, 128) >= 192) id = dma ? (a.M >= 150000 ? 41 : 12) : 2;  // tall M: 16x16x32 +6 %
+    else if (tiles(256, 128) >= 192) id = dma ? (a.Mp >= 150000 ? 41 : 12) : 2;  // tall M: 16x16x32 +6 %
     else if (tiles(64, 128) >= 192) id = dma ? 13 : 3;
     else id = dma ? 14 : 4;
     req = 1;
@@ -341,7 +375,7 @@ int plan_conv(const ConvArgs& a, int planes, const ConvOverrides& o, ConvPlan* p
     return plan_glds_tile(a, planes, *t, req, p);
   }
   const int r = (id >= 1 && id <= 6) ? id : 4;
-  const int64_t nt = tiles(kRegTile[r][0], kRegTile[r][1]);
+  const int64_t nt = tiles_of(a, kRegTile[r][0], kRegTile[r][1]);
   if (nt > 0x7fffffff) {
     set_error("sp_conv2d: %lld tiles exceed the grid", (long long)nt);
     return -1;
@@ -412,6 +446,9 @@ extern "C" int sp_set_tuning(int knob, int value) {
     case SP_TUNE_GLDS_EPILOGUE:
       sp::g_overrides.glds_epv = value == 4 ? 4 : -1;
       return 0;
+    case SP_TUNE_FOLD:
+      sp::g_plan_batch.fold = value == 1 || value == 2 ? value : 0;
+      return 0;
     case SP_TUNE_MSDA_GENERIC:
       sp::set_msda_generic(value == 1 ? 1 : 0);
       return 0;
@@ -419,4 +456,18 @@ extern "C" int sp_set_tuning(int knob, int value) {
       sp::set_error("sp_set_tuning: unknown knob %d", knob);
       return -1;
   }
+}
+
+// Batch-invariant planning (product path; per thread like the overrides above): while batch > 0, every launch
+// of `batch` images is planned as one of `plan_batch` images. (0, 0) restores planning from the launch's own rows.
+extern "C" int sp_set_plan_batch(int batch, int plan_batch) {
+  if (batch == 0 && plan_batch == 0) {
+    sp::g_plan_batch.batch = sp::g_plan_batch.plan = 0;
+    return 0;
+  }
+  SP_ARG_CHECK(batch >= 1 && plan_batch >= 1, "sp_set_plan_batch: batch %d, plan_batch %d (both >= 1, or 0, 0)", batch,
+               plan_batch);
+  sp::g_plan_batch.batch = batch;
+  sp::g_plan_batch.plan = plan_batch;
+  return 0;
 }

@@ -395,7 +395,10 @@ int wino_plan(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino, 
                               &w->T))
     return rc;
   const int64_t T = w->T;
-  w->in_vw = MT == 2 ? 4 : wino43_in_vw(T * d->Cin);
+  // every size rule below reads Tp, the tiles this launch is planned as (T, or sp_set_plan_batch's share of it)
+  int64_t Tp;
+  if (plan_rows(what, T, &Tp)) return -1;
+  w->in_vw = MT == 2 ? 4 : wino43_in_vw(Tp * d->Cin);
   w->out_vw = MT == 2 ? 4 : wino43_out_vw();
   w->planes = d->precision == SP_PREC_BF16 ? 1 : d->precision == SP_PREC_F32X2 ? 2 : 3;
   if (!gemm) return 0;
@@ -422,6 +425,7 @@ int wino_plan(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino, 
   g.d.Wt_bf16 = wt_wino;
   g.d.wt_plane_stride = wino_plane_stride;
   g.M = T;
+  g.Mp = Tp;
   g.K = d->Cin;
   g.HoWo = (int32_t)T;
   g.fast = 1;
@@ -450,9 +454,9 @@ int wino_plan(const char* what, const sp_conv_desc* d, const uint16_t* wt_wino, 
     // short batches (the bs1 80² maps, 14400 rows; not the bs32 20² maps at 28800): 256×128 with eight 32×128
     // waves for Cout >= 256 (0.0395 vs 0.0535 ms for 245 at 80²×384), else 64×64 (0.0103 vs 0.0114 for 246 at
     // 80²×128; profiles/r5/bs1/tune_bs1_cross.json)
-    if (d->Cout % 128 == 0 && T * NC >= 12000 && T * NC < 20000) cfg = d->Cout >= 256 ? 63 : 14;
-    else if (d->Cout % 128 || T * NC < 12000) cfg = 14;
-    else if (T * NC >= 400000 && d->Cout >= 384) cfg = 247;
+    if (d->Cout % 128 == 0 && Tp * NC >= 12000 && Tp * NC < 20000) cfg = d->Cout >= 256 ? 63 : 14;
+    else if (d->Cout % 128 || Tp * NC < 12000) cfg = 14;
+    else if (Tp * NC >= 400000 && d->Cout >= 384) cfg = 247;
     else if (d->Cout <= 256) cfg = 246;
     else cfg = 245;
   }

@@ -7,7 +7,8 @@ Only module-scope lines change; the Ray Serve deployment class AmenitiesDetector
 reference's text byte for byte (tests/test_dropin_reference.py compares it). The model and processor built
 at import (serve.py:203-204) become the spotter_amd objects (the model's operand precision from the
 SPOTTER_PRECISION environment variable, default "fp32"; an unknown value fails the import; serve.py already
-imports os, :5), and serve.py's module-global `Image` (bound by
+imports os, :5; the opt-in SPOTTER_BATCHING and SPOTTER_BATCH_INVARIANT are read by from_pretrained itself, so they
+need no text in serve.py and fail its import the same way when malformed), and serve.py's module-global `Image` (bound by
 `from PIL import Image, ImageDraw`, serve.py:10) is rebound to spotter_amd.jpeg.image_module(): Pillow's
 module with a GPU `open` (JPEGs decoded on the GPU, pixels identical to Pillow's; Pillow parses the header
 first, so every file Pillow refuses raises exactly as before) whose decoded images also encode on the GPU

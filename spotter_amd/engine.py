@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .config import PRECISIONS, SpotterConfig, check_precision
+from .config import PRECISIONS, SpotterConfig, check_batch_invariant, check_precision
 from .ops import V, view
 from .weights import backbone_plan
 
@@ -152,10 +152,16 @@ class Engine:
                  fuse_ln: bool = False, winograd: str | bool = "auto", wino_m: int = 4,
                  bf16_store: bool | None = None, direct_c32: bool = True,
                  direct_c64_bf16: bool = True, splitk_combine: bool = False, direct_c64_x3: bool = True,
-                 direct_c32_x3: bool = False):
+                 direct_c32_x3: bool = False, batch_invariant: int | None = None):
         from ._lib import SP_BUILD_FUSED_LN, lib
 
         check_precision(precision)
+        # batch_invariant=P (an int >= 1; None = off): every forward of B images is planned as a forward of P
+        # images, so an image's logits and boxes are the same bits whatever B is and whichever slot it takes
+        # (DESIGN 5.19). The library plans every GEMM / Winograd launch for rows · P / B (sp_set_plan_batch, set
+        # around every forward and graph capture), and every size gate of this file reads self._pb(B) = P in place
+        # of B. Not invariant across different P, precisions or library builds.
+        self.batch_invariant = check_batch_invariant(batch_invariant)
         self.cfg = cfg
         self.fold_repvgg = fold_repvgg
         self.fuse_shortcut = fuse_shortcut  # bottleneck tail + projection shortcut as one GEMM (_fused_tail)
@@ -240,6 +246,7 @@ class Engine:
             raise RuntimeError(f"sp_device_init: {lib().sp_last_error().decode()}")
         with torch.cuda.device(self.dev):
             self._pack(weights)
+        self._B = 1  # images of the slice being launched (_plan_batch)
         self._ws = {}
         self._consts = {}
         self._ctxs = {}
@@ -469,10 +476,21 @@ class Engine:
 
     SPLITK_COUNTERS = 4096  # arrival counters per context: one per output tile of a split-K launch
 
+    def _pb(self, B: int) -> int:
+        """The batch every size gate is evaluated for: B, or P under batch_invariant=P."""
+        return B if self.batch_invariant is None else self.batch_invariant
+
     def _splitk(self) -> dict:
         """The split-K scratch of this context's GEMM launches: the partial-sum workspace and, with
         splitk_combine, the arrival counters (zeroed once here; every launch leaves them zero)."""
-        kw = {"workspace": self._buf("splitk", self.SPLITK_ELEMS)}
+        n = self.SPLITK_ELEMS
+        if self.batch_invariant is not None:
+            # the factor is planned for P images and the slabs hold the launch's own rows (splits × actual M): a
+            # P-image launch needs under 2048 tiles × 4096 = 8 M elements (conv_plan.hip split_for: splits × tiles
+            # stays below twice SP_SPLITK_BLOCKS), so SPLITK_ELEMS never lowers a P-image factor, and
+            # ceil(B / P) times as much holds the same factor on B images
+            n *= -(-self._B // self.batch_invariant)
+        kw = {"workspace": self._buf("splitk", n)}
         if self.splitk_combine:
             c = self._ws.get("splitk_cnt")
             if c is None:
@@ -512,7 +530,7 @@ class Engine:
     def _cv(self, x: V, n, h, w, cw: ConvW, stride, out: V, act=None, res1=None, res2=None, **kw):
         pad = cw.k // 2
         if (cw.cin == 64 and cw.cout == 64 and cw.k == 3 and stride == 1 and not kw and res2 is None
-                and act in ("relu", None) and n * h * w >= self.C64_MIN_PIXELS):
+                and act in ("relu", None) and self._pb(n) * h * w >= self.C64_MIN_PIXELS):
             rows16 = lambda v: v.ld % 8 == 0 and v.off % 8 == 0  # noqa: E731 (16-byte aligned bf16 rows)
             if (self.direct_c64_bf16 and x.is_bf16 and out.is_bf16 and cw.mode == "bf16" and rows16(x)
                     and rows16(out) and (res1 is None or (res1.is_bf16 and rows16(res1)))):
@@ -523,7 +541,7 @@ class Engine:
             if self.direct_c64_x3 and cw.mode == "x3" and res1 is None and rows4(x) and rows4(out):
                 # the fp32 path's stage-0 3x3: the direct split kernel, bit-identical to the x3 implicit GEMM
                 return ops.conv3x3_c64_x3(x, cw.w16, cw.scale, cw.shift, out, n, h, w, act=act)
-        if cw.wino is not None and stride == 1 and not kw and not x.is_bf16 and self._wino_pays(n * h * w, cw.cin):
+        if cw.wino is not None and stride == 1 and not kw and not x.is_bf16 and self._wino_pays(self._pb(n) * h * w, cw.cin):
             wm = self.wino_m
             tiles = n * ((h + wm - 1) // wm) * ((w + wm - 1) // wm)
             work = self._buf("wino_work", ops.wino_work_elems(wm, tiles, cw.cin, cw.cout))
@@ -552,7 +570,8 @@ class Engine:
             ops.linear(x, rows, lw.k, lw.w, lw.n, tmp, bias=lw.b, act=act, res1=res1, res2=res2, a2=a2,
                        row_scale=row_scale, **self._splitk(), **_wkw(lw.w16))
             return ops.layernorm(tmp, *ln, out, rows, lw.n, self.cfg.layer_norm_eps)
-        sk = self._splitk() if rows > self.splitk_min_rows else {}
+        prows = rows if self.batch_invariant is None else rows // self._B * self.batch_invariant
+        sk = self._splitk() if prows > self.splitk_min_rows else {}
         return ops.linear(x, rows, lw.k, lw.w, lw.n, out, bias=lw.b, act=act, res1=res1, res2=res2, a2=a2,
                           row_scale=row_scale, **sk, **_wkw(lw.w16))
 
@@ -613,13 +632,13 @@ class Engine:
                 ops.conv3x3_c32_bf16(view(src, cw.cin), cw.w16, cw.scale, cw.shift, view(dst, cw.cout), B, h1, w1,
                                      cw.cout, act=self.act_bb)
             elif (c32 and self.direct_c32_x3 and cw.x3p is not None and self.precision == "fp32"
-                  and B * h1 * w1 >= self.C32_MIN_PIXELS):
+                  and self._pb(B) * h1 * w1 >= self.C32_MIN_PIXELS):
                 # precision "fp32": the direct kernel on the 3-way split (bf16 MFMA pipe) instead of exact fp32
                 # products; "fp32-mfma" keeps sp_conv3x3_c32 below
                 ops.conv3x3_c32_x3(view(src, cw.cin), cw.x3p, cw.scale, cw.shift, view(dst, cw.cout), B, h1, w1,
                                    cw.cout, act=self.act_bb)
             elif (c32 and self.direct_c32 and cw.mode == "f32" and not self.bf16_store
-                  and B * h1 * w1 >= self.C32_MIN_PIXELS):
+                  and self._pb(B) * h1 * w1 >= self.C32_MIN_PIXELS):
                 # the fp32 modes: the same direct kernel on fp32 rows with fp32 MFMAs (exact products): 1.24-1.29x
                 # the fp32-MFMA GEMM at bs32 (113 / 128 TF), 1.08-1.17x at bs8 of 320²
                 # (profiles/r3/x3/ab_stem_c32_f32.jsonl); smaller maps (a few tiles per CU at most for its
@@ -818,11 +837,34 @@ class Engine:
             raise ValueError("Make sure that the channel dimension of the pixel values match with the one set in the configuration.")
         nmb = self.micro_batches_for(B) if microbatches is None else microbatches
         nmb = max(1, min(nmb, B))
+        if self.batch_invariant is None:
+            return self._forward(pixel_values, nmb)
+        # batch_invariant=P: each micro-batch slice is planned as P images by its own sp_set_plan_batch (_run)
+        try:
+            return self._forward(pixel_values, nmb)
+        finally:
+            self._plan_batch(0)
+
+    def _plan_batch(self, B: int):
+        """sp_set_plan_batch(B, P) for the launches that follow on this thread (B = 0: reset), and the B the size
+        gates of this file divide row counts by."""
+        from ._lib import lib
+
+        self._B = max(B, 1)
+        if self.batch_invariant is None:
+            return
+        if lib().sp_set_plan_batch(B, self.batch_invariant if B else 0) != 0:
+            raise RuntimeError(f"sp_set_plan_batch: {lib().sp_last_error().decode()}")
+
+    def _forward(self, pixel_values, nmb):
+        cfg = self.cfg
+        B = pixel_values.shape[0]
         Q, NC = cfg.num_queries, cfg.num_labels
         with torch.cuda.device(self.dev):
             out_logits = self._out("logits", B * Q * NC).view(B, Q, NC)
             out_boxes = self._out("boxes", B * Q * 4).view(B, Q, 4)
             if nmb == 1:
+                self._plan_batch(B)
                 for _ in self._run(pixel_values, out_logits, out_boxes):
                     pass
                 return out_logits, out_boxes
@@ -833,7 +875,7 @@ class Engine:
                 ctx = self._ctx(i)
                 ctx["stream"].wait_stream(main)
                 b0, b1 = bounds[i], bounds[i + 1]
-                jobs.append([ctx, self._run(pixel_values[b0:b1], out_logits[b0:b1], out_boxes[b0:b1])])
+                jobs.append([ctx, self._run(pixel_values[b0:b1], out_logits[b0:b1], out_boxes[b0:b1]), b1 - b0])
             saved = self._ws
             # job i starts on the GPU only after job i-1 has issued `stagger` residual blocks
             # (stream event), so the slices' GEMM tails do not line up.
@@ -844,13 +886,14 @@ class Engine:
                     for ji, job in enumerate(jobs):
                         if job is None:
                             continue
-                        ctx, g = job
+                        ctx, g, nb = job
                         if ji > 0 and steps[ji] == 0:
                             if gate[ji - 1] is None and jobs[ji - 1] is not None:
                                 continue
                             if gate[ji - 1] is not None:
                                 ctx["stream"].wait_event(gate[ji - 1])
                         self._ws = ctx["ws"]
+                        self._plan_batch(nb)  # the slices interleave and may differ in size: set per step
                         with torch.cuda.stream(ctx["stream"]):
                             try:
                                 next(g)
@@ -870,7 +913,7 @@ class Engine:
         """Streams a batch of B images is split over (the served path and bench.py share this)."""
         if self.microbatches is not None:
             return self.microbatches
-        return 1
+        return 1  # no rule on B here: under batch_invariant nothing to replace (any split gives the same bits)
 
     def _ctx(self, i):
         c = self._ctxs.get(i)

@@ -15,7 +15,7 @@ from dataclasses import dataclass
 
 import torch
 
-from .config import PRESETS, SpotterConfig, check_precision
+from .config import PRESETS, SpotterConfig, batch_invariant_from_env, check_batch_invariant, check_precision
 from .shared_batch import batching_from_env, check_batching, default_socket
 
 
@@ -52,8 +52,11 @@ class SpotterForObjectDetection:
 
     def __init__(self, cfg: SpotterConfig, weights: dict | None = None, seed: int = 0,
                  use_graphs: bool = True, precision: str = "fp32", batching: bool | str = False,
-                 max_batch: int = 32, max_wait_ms: float = 2.0):
-        """batching: True or "threads" coalesces concurrent calls (several request threads) into one engine forward
+                 max_batch: int = 32, max_wait_ms: float = 2.0, batch_invariant: int | None = None):
+        """batch_invariant: None (default), or the plan batch P >= 1 of the batch-invariant mode (Engine documents it):
+        an image's logits and boxes are then the same bits whatever else shares its forward. Checked here, pickled
+        with the model, and part of what a shared-batch owner compares when this replica attaches.
+        batching: True or "threads" coalesces concurrent calls (several request threads) into one engine forward
         (spotter_amd.batching.MicroBatcher, up to max_batch images within max_wait_ms); "shared" hands every call to
         the one engine owner process of this GPU (spotter_amd.shared_batch), which coalesces the calls of all the
         replica processes on it: this object then builds no engine. False or "off": neither. Anything else raises
@@ -71,6 +74,7 @@ class SpotterForObjectDetection:
         # config.PRECISIONS key; "fp32" = the fp32-accurate parity path, "bf16" = the C4 variant. Checked here, at
         # construction (serve.py import time), so a bad SPOTTER_PRECISION fails the deployment, not the first request.
         self.precision = check_precision(precision)
+        self.batch_invariant = check_batch_invariant(batch_invariant)
         self._graphs = {}
         self._seen = set()
         self.config = _Config(cfg)
@@ -93,11 +97,15 @@ class SpotterForObjectDetection:
         os.environ.get("SPOTTER_PRECISION", "fp32") (deploy/rayservice-template.yaml sets "bf16" for C4).
         HF's own from_pretrained has no such input; the weights loaded are the same either way.
         batching: as the constructor's; when it is not given, the SPOTTER_BATCHING environment variable (off,
-        threads or shared) decides, so a deployment turns batching on without a change to serve.py."""
+        threads or shared) decides, so a deployment turns batching on without a change to serve.py.
+        batch_invariant: as the constructor's; when it is not given, SPOTTER_BATCH_INVARIANT (off, 0 or an integer
+        >= 1) decides, the same way."""
         check_precision(precision)
         kw["precision"] = precision
         if "batching" not in kw:
             kw["batching"] = batching_from_env()
+        if "batch_invariant" not in kw:  # SPOTTER_BATCH_INVARIANT, read here like SPOTTER_BATCHING: a malformed
+            kw["batch_invariant"] = batch_invariant_from_env()  # value fails serve.py's import, not a request
         if name_or_path.startswith("synthetic:"):
             synthetic, name_or_path = True, name_or_path[len("synthetic:"):]
         if synthetic:
@@ -152,7 +160,8 @@ class SpotterForObjectDetection:
 
                     dev = self._device or torch.device("cuda", torch.cuda.current_device())
                     self._engine = Engine(self.cfg, self._host_weights(), dev,
-                                          precision=getattr(self, "precision", "fp32"))
+                                          precision=getattr(self, "precision", "fp32"),
+                                          batch_invariant=getattr(self, "batch_invariant", None))
         return self._engine
 
     # -- forward ------------------------------------------------------------------
@@ -197,7 +206,8 @@ class SpotterForObjectDetection:
                     opts.update(getattr(self, "_shared_opts", {}))
                     self._shared = SharedBatchClient(
                         self.cfg, self.precision, name, lambda: weights_digest(self._host_weights()),
-                        default_socket(idx), device_index=idx, revision=getattr(self, "_revision", None), **opts)
+                        default_socket(idx), device_index=idx, revision=getattr(self, "_revision", None),
+                        batch_invariant=getattr(self, "batch_invariant", None), **opts)
         return self._shared
 
     def _run(self, pixel_values):

@@ -392,6 +392,15 @@ def conv_plan(desc) -> dict:
 
 
 TUNE_GLDS_EPILOGUE = 3  # include/spotter_hip.h sp_tuning_knob
+TUNE_FOLD = 5  # the folded split-K tile: 1 = never, 2 = every split the register-staged 64×64 tile runs
+
+
+def set_plan_batch(batch: int = 0, plan_batch: int = 0):
+    """sp_set_plan_batch for this thread's later launches and plan queries: rows of `batch` images planned as
+    `plan_batch` images; (0, 0) restores planning from the launch's own rows."""
+    from ._lib import call
+
+    call("sp_set_plan_batch", int(batch), int(plan_batch))
 
 
 def set_tuning(knob: int, value: int | None):

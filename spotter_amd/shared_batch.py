@@ -14,7 +14,7 @@ launches per batch (gather the B slot images into the contiguous [B,3,H,W] input
 boxes into its slot) read and write the slots directly.
 
 Messages (multiprocessing.connection over an AF_UNIX socket, all tiny):
-    ("hello", {config, precision, digest, shm, in_elems})  -> ("ok", {pid, stub}) | ("refused", field, text)
+    ("hello", {config, precision, batch_invariant, digest, shm, in_elems})  -> ("ok", {pid, stub}) | ("refused", field, text)
     ("submit", seq, (H, W))                                -> ("done", seq, error or None)
     ("stats",)                                             -> ("stats", {batches, images, max_batch, clients})
 
@@ -190,9 +190,10 @@ class _Peer:
 
 class Owner:
     def __init__(self, a):
-        from .config import PRESETS, check_precision
+        from .config import PRESETS, check_batch_invariant, check_precision
 
         self.a = a
+        self.batch_invariant = check_batch_invariant(a.batch_invariant or None)  # 0 on the command line = off
         self.stub = a.stub
         self.max_batch = max(1, min(a.max_batch, MAX_BATCH_LIMIT))
         self.max_wait = a.max_wait_ms / 1e3
@@ -215,6 +216,7 @@ class Owner:
             self.dev = torch.device("cuda", a.device)
             kw = {"revision": a.revision} if a.revision else {}
             self.model = SpotterForObjectDetection.from_pretrained(a.model, precision=self.precision, batching=False,
+                                                                   batch_invariant=self.batch_invariant,
                                                                    **kw).to(self.dev)
             self.cfg = self.model.cfg
             self.digest = weights_digest(self.model._host_weights())
@@ -229,6 +231,9 @@ class Owner:
                 return ("refused", f"config.{k}", f"owner has {mine.get(k)!r}, client has {theirs.get(k)!r}")
         if h.get("precision") != self.precision:
             return ("refused", "precision", f"owner runs {self.precision!r}, client asks {h.get('precision')!r}")
+        if h.get("batch_invariant") != self.batch_invariant:  # another plan batch gives other bits
+            return ("refused", "batch_invariant",
+                    f"owner runs {self.batch_invariant!r}, client asks {h.get('batch_invariant')!r}")
         if self.digest is not None and h.get("digest") != self.digest:
             return ("refused", "digest", "the client's host weights are not the owner's")
         in_elems = int(h.get("in_elems", 0))
@@ -420,6 +425,7 @@ def main(argv=None) -> int:
     ap.add_argument("--model", required=True)
     ap.add_argument("--revision", default=None)
     ap.add_argument("--precision", default="fp32")
+    ap.add_argument("--batch-invariant", type=int, default=0, help="plan batch P of the batch-invariant mode; 0 = off")
     ap.add_argument("--max-batch", type=int, default=16)
     ap.add_argument("--max-wait-ms", type=float, default=2.0)
     ap.add_argument("--idle-exit-s", type=float, default=60.0)
@@ -441,8 +447,9 @@ class SharedBatchClient:
     def __init__(self, cfg, precision: str, model_name: str | None, digest_fn, socket_path: str, device_index: int = 0,
                  revision: str | None = None, max_batch: int = 16, max_wait_ms: float = 2.0,
                  idle_exit_s: float = 60.0, timeout_s: float = 30.0, start_timeout_s: float = 300.0,
-                 stub: bool = False):
+                 stub: bool = False, batch_invariant: int | None = None):
         self.cfg, self.precision, self.model_name, self.revision = cfg, precision, model_name, revision
+        self.batch_invariant = batch_invariant
         self._digest_fn, self._digest = digest_fn, None
         self.socket_path, self.device_index = socket_path, device_index
         self.max_batch, self.max_wait_ms, self.idle_exit_s = max_batch, max_wait_ms, idle_exit_s
@@ -467,6 +474,8 @@ class SharedBatchClient:
         cmd = [sys.executable, "-m", "spotter_amd.shared_batch", "--device", str(self.device_index), "--socket",
                self.socket_path, "--model", self.model_name, "--precision", self.precision, "--max-batch",
                str(self.max_batch), "--max-wait-ms", str(self.max_wait_ms), "--idle-exit-s", str(self.idle_exit_s)]
+        if self.batch_invariant:
+            cmd += ["--batch-invariant", str(self.batch_invariant)]
         if self.revision:
             cmd += ["--revision", self.revision]
         if self.stub:
@@ -558,6 +567,7 @@ class SharedBatchClient:
         if self._digest is None:
             self._digest = self._digest_fn() if not self.stub else "stub"
         self._send(("hello", {"config": self.cfg.to_json(), "precision": self.precision, "digest": self._digest,
+                              "batch_invariant": self.batch_invariant,
                               "shm": self._slot.shm.name, "in_elems": self._slot.in_elems}), "hello")
         r = self._recv(self.timeout_s, "hello")
         if r[0] == "refused":

@@ -6,6 +6,9 @@ against batch 1 and between the images of the batch. Any batcher (spotter_amd/ba
 a caller rows computed at whatever B it rode in, so this is what its outputs can differ by from a bs1 call.
 
     python tools/batch_size_probe.py --out profiles/shared_batch/batch_size_probe.json
+    python tools/batch_size_probe.py --batch-invariant 1 --out profiles/batch_invariant/batch_size_probe_inv1.json
+
+With --batch-invariant P every |Δscore| is 0.0 and the counts agree at every B.
 """
 from __future__ import annotations
 
@@ -30,13 +33,15 @@ def main():
     ap.add_argument("--preset", default="r101vd")
     ap.add_argument("--precision", nargs="+", default=["bf16", "fp32"])
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 2, 3, 4, 6, 8, 12])
+    ap.add_argument("--batch-invariant", type=int, default=0, help="Engine(batch_invariant=P); 0 = off (the default mode)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     im = Image.open(os.path.join(ROOT, "tests", "golden", "test_pic.jpg")).convert("RGB")
     x = SpotterImageProcessor()(images=im)["pixel_values"]
     out = {}
     for prec in a.precision:
-        m = SpotterForObjectDetection(PRESETS[a.preset], precision=prec, use_graphs=False)
+        m = SpotterForObjectDetection(PRESETS[a.preset], precision=prec, use_graphs=False,
+                                      batch_invariant=a.batch_invariant or None)
         rows, base = {}, None
         for b in a.batch:
             with torch.no_grad():

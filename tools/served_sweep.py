@@ -96,7 +96,8 @@ def compare_outputs(ref, got):
     return None
 
 
-def worker(preset: str, precision: str, warmup: int, check: bool = False, reference: bool = False):
+def worker(preset: str, precision: str, warmup: int, check: bool = False, reference: bool = False,
+           batch_invariant: int | None = None):
     import asyncio
 
     import httpx
@@ -113,7 +114,7 @@ def worker(preset: str, precision: str, warmup: int, check: bool = False, refere
     from spotter_amd.shared_batch import batching_from_env
 
     model = SpotterForObjectDetection(PRESETS[preset], use_graphs=True, precision=precision,
-                                      batching=batching_from_env())
+                                      batching=batching_from_env(), batch_invariant=batch_invariant)
     proc = SpotterImageProcessor()
     seen = _recording(proc) if check or reference else None
     body = json.dumps({"image_urls": [url]}).encode()
@@ -154,11 +155,11 @@ def worker(preset: str, precision: str, warmup: int, check: bool = False, refere
     print("RESULT " + json.dumps(res), flush=True)
 
 
-def reference_outputs(preset: str, precision: str, timeout: float):
+def reference_outputs(preset: str, precision: str, timeout: float, batch_invariant: int | None = None):
     """(labels, boxes) of the fixture from ONE process without batching: what every checked response must equal."""
     env = dict(os.environ, SPOTTER_BATCHING="off")
     p = subprocess.run([sys.executable, "-u", os.path.abspath(__file__), "--worker", "--reference", "--preset", preset,
-                        "--precision", precision, "--warmup", "1"], capture_output=True, text=True, env=env, cwd=ROOT,
+                        "--precision", precision, "--warmup", "1", *_bi(batch_invariant)], capture_output=True, text=True, env=env, cwd=ROOT,
                        timeout=timeout)
     line = next((l for l in p.stdout.splitlines() if l.startswith("RESULT ")), None)
     if p.returncode != 0 or line is None:
@@ -167,6 +168,11 @@ def reference_outputs(preset: str, precision: str, timeout: float):
     if len(outs) != 1:
         raise RuntimeError(f"reference run gave {len(outs)} different outputs for one request")
     return outs[0][0]
+
+
+def _bi(batch_invariant):
+    """The worker's command-line form of the batch-invariant setting."""
+    return ["--batch-invariant", str(batch_invariant)] if batch_invariant else []
 
 
 def _owner_stats(sock: str):
@@ -180,7 +186,7 @@ def _owner_stats(sock: str):
 
 
 def sweep_point(k: int, precision: str, preset: str, seconds: float, warmup: int, timeout: float,
-                stub_ms: float | None = None, batching: str = "off", reference=None):
+                stub_ms: float | None = None, batching: str = "off", reference=None, batch_invariant=None):
     import numpy as np
 
     env = dict(os.environ)
@@ -193,7 +199,7 @@ def sweep_point(k: int, precision: str, preset: str, seconds: float, warmup: int
         extra.append("--check-outputs")
     procs = [subprocess.Popen([sys.executable, "-u", os.path.abspath(__file__), "--worker", "--preset", preset,
                                "--precision", precision,
-                               "--warmup", str(warmup), *extra],
+                               "--warmup", str(warmup), *extra, *_bi(batch_invariant)],
                               stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env=env, cwd=ROOT)
              for _ in range(k)]
     try:
@@ -230,7 +236,7 @@ def sweep_point(k: int, precision: str, preset: str, seconds: float, warmup: int
     lat = np.array([x for r in res for x in r["lat_ms"]])
     n = int(lat.size)
     out = {"k_processes": k, "precision": precision, "preset": preset, "window_s": seconds, "batching": batching,
-           "requests": n, "img_per_s": round(n / seconds, 1),
+           "batch_invariant": batch_invariant, "requests": n, "img_per_s": round(n / seconds, 1),
            "per_process_img_per_s": [round(r["requests"] / seconds, 1) for r in res],
            "p50_ms": round(float(np.percentile(lat, 50)), 3) if n else None,
            "p95_ms": round(float(np.percentile(lat, 95)), 3) if n else None,
@@ -287,19 +293,22 @@ def main():
     ap.add_argument("--check-outputs", action="store_true",
                     help="compare every response's labels and boxes with a single-process run without batching")
     ap.add_argument("--reference", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--batch-invariant", type=int, default=0,
+                    help="plan batch P of the batch-invariant mode for every replica, the owner and the reference; 0 = off")
     a = ap.parse_args()
     if a.worker:
         if a.stub_ms is not None:
             return stub_worker(a.stub_ms)
-        return worker(a.preset, a.precision[0], a.warmup, a.check_outputs, a.reference)
+        return worker(a.preset, a.precision[0], a.warmup, a.check_outputs, a.reference, a.batch_invariant or None)
     if max(a.k) > 12:
         raise SystemExit("at most 12 processes per GPU (the box allows 16 GPU processes in all)")
     for prec in a.precision:
-        ref = reference_outputs(a.preset, prec, a.timeout) if a.check_outputs else None
+        ref = reference_outputs(a.preset, prec, a.timeout, a.batch_invariant) if a.check_outputs else None
         pts = {b: [] for b in a.batching}
         for k in a.k:
             for b in a.batching:
-                r = sweep_point(k, prec, a.preset, a.seconds, a.warmup, a.timeout, batching=b, reference=ref)
+                r = sweep_point(k, prec, a.preset, a.seconds, a.warmup, a.timeout, batching=b, reference=ref,
+                                batch_invariant=a.batch_invariant or None)
                 print(json.dumps(r), flush=True)
                 pts[b].append(r)
         for b in a.batching:
@@ -312,7 +321,8 @@ def main():
                    "points": pts[b], "best_k": best["k_processes"], "best_img_per_s": best["img_per_s"]}
             if a.out:
                 os.makedirs(a.out, exist_ok=True)
-                name = f"served_{a.preset}_{prec}" + ("" if b == "off" else f"_{b}") + ".json"
+                name = (f"served_{a.preset}_{prec}" + ("" if b == "off" else f"_{b}")
+                        + (f"_inv{a.batch_invariant}" if a.batch_invariant else "") + ".json")
                 with open(os.path.join(a.out, name), "w") as f:
                     json.dump(doc, f, indent=1)
         bad = [r for b in a.batching for r in pts[b] if r.get("responses_mismatched")]

@@ -300,6 +300,33 @@ typedef struct {
 int sp_winograd_plan(const sp_conv_desc* d, int wm, int64_t wino_plane_stride, int64_t work_elems,
                      sp_winograd_plan_info* out);
 
+/* The F(4x4) output transform of a 3x3 conv fused into the 1x1 conv that reads it (additive to ABI v20): a
+ * bottleneck's conv2 → expand. conv2 and work / work_elems as sp_winograd_f43_output takes them (M already in the
+ * workspace: the input and gemm stages have run); expand: the descriptor sp_conv2d would take for the 1x1, with
+ * A = conv2's C, lda = its ldc, Cin = its Cout and the same N, H, W (refused otherwise). expand_frag: the expand's
+ * hi / mid / lo planes repacked into MFMA fragment order, [Cout/32][K/16][3][64][8] bf16 with element
+ * (nb, s, plane, lane, j) = planes[plane][32 nb + lane % 32][16 s + 8 (lane / 32) + j], frag_elems = 3*Cout*K
+ * (16-byte aligned); NULL: never fused.
+ * The expand is planned like every sp_conv2d launch (the calling thread's overrides, sp_set_plan_batch). Where
+ * the plan is an LDS-DMA tile on 32x32x16 MFMAs with three planes and no split-K, K is 128 or 256,
+ * Cout % 32 == 0, the expand has no res2 / A2 / row_scale / grouped rows / bf16 rows, conv2 no residual, and the
+ * planned rows N*H*W reach min_pixels, ONE persistent kernel computes the expand's output from M, bit-identical to
+ * the two launches, and conv2's C rows are NOT written. Otherwise the call is sp_winograd_f43_output(conv2) then the
+ * expand's planned launch. sp_winograd_expand_plan says which, without a launch or a device call (has_frag: whether
+ * expand_frag would be given); both run the same function. */
+typedef struct {
+  sp_conv_plan_info expand; /* the expand's own plan (what the unfused path launches) */
+  int32_t fused;            /* 1: the fused kernel runs; 0: output transform + the plan above */
+  int32_t reserved;
+  int64_t tiles;            /* conv2's Winograd tiles T */
+  int64_t units;            /* 32-pixel work units of the fused kernel: ceil(T / 2) */
+} sp_winograd_expand_plan_info;
+int sp_winograd_f43_expand(const sp_conv_desc* conv2, const float* work, int64_t work_elems,
+                           const sp_conv_desc* expand, const uint16_t* expand_frag, int64_t frag_elems,
+                           int64_t min_pixels, void* stream);
+int sp_winograd_expand_plan(const sp_conv_desc* conv2, int64_t work_elems, const sp_conv_desc* expand, int has_frag,
+                            int64_t min_pixels, sp_winograd_expand_plan_info* out);
+
 /* NCHW → NHWC (pixel_values layout of the processor contract → conv layout). */
 int sp_nchw_to_nhwc(const float* x, float* y, int n, int c, int h, int w, void* stream);
 /* Backbone stem conv 1 (RN:71-114: 3x3 stride 2 pad 1, Cin 3, FrozenBN affine M2:748-758, ReLU)

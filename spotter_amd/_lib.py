@@ -57,6 +57,10 @@ class SpWinogradPlanInfo(C.Structure):
     _fields_ = [("gemm", SpConvPlanInfo), ("components", i32), ("in_vw", i32), ("out_vw", i32), ("tiles", i64)]
 
 
+class SpWinogradExpandPlanInfo(C.Structure):
+    _fields_ = [("expand", SpConvPlanInfo), ("fused", i32), ("reserved", i32), ("tiles", i64), ("units", i64)]
+
+
 class SpMsdaDesc(C.Structure):
     _fields_ = [
         ("value", vp), ("ld_value", i64), ("value_col", i32),
@@ -148,6 +152,9 @@ _SIGS = {
     "sp_winograd_f43_input": (i32, [C.POINTER(SpConvDesc), vp, i64, vp]),
     "sp_winograd_f43_gemm": (i32, [C.POINTER(SpConvDesc), vp, i64, vp, i64, vp]),
     "sp_winograd_f43_output": (i32, [C.POINTER(SpConvDesc), vp, i64, vp]),
+    "sp_winograd_f43_expand": (i32, [C.POINTER(SpConvDesc), vp, i64, C.POINTER(SpConvDesc), vp, i64, i64, vp]),
+    "sp_winograd_expand_plan": (i32, [C.POINTER(SpConvDesc), i64, C.POINTER(SpConvDesc), i32, i64,
+                                      C.POINTER(SpWinogradExpandPlanInfo)]),
     "sp_nchw_to_nhwc": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "sp_stem_conv3x3s2_nchw": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "sp_maxpool3x3s2": (i32, [vp, vp, i64, i32, i32, i32, i32, vp]),

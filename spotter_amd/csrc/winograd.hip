@@ -533,6 +533,14 @@ int wino_plan_info(const sp_conv_desc* d, int64_t wino_plane_stride, int64_t wor
 }  // namespace
 }  // namespace sp
 
+// wino_expand.hip: the F(4×4) output stage's argument checks and tile grid for conv2's descriptor
+namespace sp {
+int wino43_geometry(const char* what, const sp_conv_desc* d, const float* work, int64_t work_elems, bool ptrs,
+                    int* th, int* tw, int64_t* T) {
+  return wino_check<4>(what, d, nullptr, 0, work, work_elems, false, ptrs, th, tw, T);
+}
+}  // namespace sp
+
 extern "C" int sp_winograd_f23_input(const sp_conv_desc* d, float* work, int64_t work_elems, void* stream) {
   return sp::wino_input<2>("sp_winograd_f23_input", d, work, work_elems, stream);
 }

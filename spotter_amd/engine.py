@@ -76,7 +76,7 @@ def _wkw(wq):
 
 
 class ConvW:
-    __slots__ = ("w", "cin", "cout", "k", "scale", "shift", "w16", "host", "wino", "mode", "x3p")
+    __slots__ = ("w", "cin", "cout", "k", "scale", "shift", "w16", "host", "wino", "mode", "x3p", "xfrag")
 
     def __init__(self, w, cin, cout, k, scale, shift, w16=None, host=None, mode="f32"):
         self.w, self.cin, self.cout, self.k, self.scale, self.shift = w, cin, cout, k, scale, shift
@@ -85,6 +85,9 @@ class ConvW:
         self.host = host  # the packed fp32 [Cout, K] weights on the host (pack-time fusions read them)
         self.wino = None  # Winograd F(2x2, 3x3) weight planes when this stride-1 3x3 runs that way
         self.x3p = None  # hi / mid / lo planes of a layer whose GEMM mode is "f32" but whose direct kernel is x3
+        # a bottleneck expand's x3 planes in MFMA fragment order (ops.pack_expand_frag_host), for the kernel that
+        # fuses conv2's F(4x4) output transform into it (sp_winograd_f43_expand)
+        self.xfrag = None
 
 
 class LinW:
@@ -152,7 +155,7 @@ class Engine:
                  fuse_ln: bool = False, winograd: str | bool = "auto", wino_m: int = 4,
                  bf16_store: bool | None = None, direct_c32: bool = True,
                  direct_c64_bf16: bool = True, splitk_combine: bool = False, direct_c64_x3: bool = True,
-                 direct_c32_x3: bool = False, batch_invariant: int | None = None):
+                 direct_c32_x3: bool = False, batch_invariant: int | None = None, wino_expand: bool = True):
         from ._lib import SP_BUILD_FUSED_LN, lib
 
         check_precision(precision)
@@ -215,6 +218,9 @@ class Engine:
         # the same conv in mode "x3" on fp32 rows (sp_conv3x3_c64_x3): direct LDS-halo kernel, bit-identical to the x3
         # implicit GEMM it replaces, 1.65x per launch at bs32
         self.direct_c64_x3 = direct_c64_x3
+        # the identity- and projected-shortcut bottlenecks whose conv2 runs as F(4x4) Winograd: its output transform
+        # fused into the expand (sp_winograd_f43_expand, bit-identical; 1.25-1.38x per launch, profiles/wino_expand/README.md)
+        self.wino_expand = wino_expand
         # under precision "fp32" only: the Cin-32 stem 3x3s on the split planes (sp_conv3x3_c32_x3, 1.49-1.59x per
         # launch) instead of the exact-product sp_conv3x3_c32. Off by default: both are fp32-accurate, but the split
         # rounds the 288-term sums differently, so the stem maps, and through the query selection the outputs,
@@ -362,6 +368,13 @@ class Engine:
                 for j, c in enumerate(blk["layers"]):
                     if c.k == 3 and (st == 1 or (lt != "bottleneck" and j == 1)):
                         self._add_wino(c)
+            c2, c3 = (blk["layers"][1], blk["layers"][2]) if lt == "bottleneck" else (None, None)
+            if (self.wino_expand and c2 is not None and c2.wino is not None and self.wino_m == 4 and st == 1
+                    and c3.mode == "x3" and c3.k == 1 and c3.cin in (128, 256) and c3.cout % 32 == 0):
+                # built for the projected-shortcut first blocks too: they take the fused kernel where the fused tail
+                # (fuse_shortcut, K = red + cin) is off
+                c3.xfrag = torch.from_numpy(ops.pack_expand_frag_host(ops.split_bf16x3_host(c3.host), c3.cout,
+                                                                      c3.cin)).to(self.dev)
             if self.fuse_shortcut and lt == "bottleneck" and (sc == "avgconv" or (sc == "conv" and st == 1)):
                 sk = pre + (".shortcut.1" if sc == "avgconv" else ".shortcut")
                 blk["fused"] = self._fused_tail(p, f"{pre}.layer.2", sk, cin)
@@ -551,6 +564,34 @@ class Engine:
                           shift=cw.shift, act=act, res1=res1, res2=res2,
                           **self._splitk(), **_wkw(cw.w16), **kw)
 
+    # sp_winograd_f43_expand's pixel gate (planned rows N·H·W): one persistent workgroup per CU over 32-pixel units,
+    # so a map of a few dozen units leaves most CUs idle. Measured per launch (profiles/wino_expand/ab_gate.json):
+    # 1600 pixels (bs1 of 40², 256 -> 1024) 0.80x the unfused pair; from 3200 (bs2 of 40²: 1.26x; bs1 of 80²,
+    # 128 -> 512: 1.52x) up to bs32 (1.25-1.38x) faster in every round
+    WINO_EXPAND_MIN_PIXELS = 3200
+
+    def _cv_wino_expand(self, x: V, n, h, w, c2: ConvW, stride, t2: V, c3: ConvW, out: V, res: V) -> bool:
+        """A bottleneck's conv2 (3×3 as F(4×4) Winograd) and expand (1×1 + residual) with conv2's output transform
+        fused into the expand (sp_winograd_f43_expand: one persistent kernel instead of the transform, the t2 round
+        trip and the GEMM; bit-identical). False where conv2 does not take the F(4×4) path or the knob is off: the
+        caller then runs the two convs as before. Where the entry point's own plan declines (tile, split-K, gate) it
+        launches the unfused pair itself, with the launch hook's accounting unchanged."""
+        if not (self.wino_expand and c3.xfrag is not None and c2.wino is not None and self.wino_m == 4 and stride == 1
+                and not x.is_bf16 and self.act_bb in ("relu", None)
+                and self._wino_pays(self._pb(n) * h * w, c2.cin)):
+            return False
+        tiles = n * ((h + 3) // 4) * ((w + 3) // 4)
+        work = self._buf("wino_work", ops.wino_work_elems(4, tiles, c2.cin, c2.cout))
+        d2, _ = ops.conv_desc(x, n, h, w, c2.cin, c2.w, c2.cout, 3, 1, 1, t2, scale=c2.scale, shift=c2.shift,
+                              act=self.act_bb)
+        stages = ops.wino_desc(d2, (c2.wino, work, 4))
+        ops.wino_launch(stages, only="input")
+        ops.wino_launch(stages, only="gemm")
+        de, hook_args = ops.conv_desc(t2, n, h, w, c3.cin, c3.w, c3.cout, 1, 1, 0, out, scale=c3.scale, shift=c3.shift,
+                                      act=self.act_bb, res1=res, **self._splitk(), **_wkw(c3.w16))
+        ops.wino_expand(stages, d2, work, de, hook_args, c3.xfrag, self.WINO_EXPAND_MIN_PIXELS)
+        return True
+
     def _lin_op(self, x: V, rows, lw: LinW, out: V, act=None, res1=None, res2=None, a2=None, row_scale=None,
                 ln=None):
         """ln = (gamma, beta): the post-norm LayerNorm of the output row fused into the GEMM epilogue
@@ -703,8 +744,9 @@ class Engine:
                 t1 = buf(f"s{s}_t1", B, h, w, red)
                 t2 = buf(f"s{s}_t2", B, ho, wo, red)
                 self._cv(view(cur, c), B, h, w, L[0], 1, view(t1, red), act=self.act_bb)
-                self._cv(view(t1, red), B, h, w, L[1], st, view(t2, red), act=self.act_bb)
-                self._cv(view(t2, red), B, ho, wo, L[2], 1, view(out, cout), act=self.act_bb, res1=res)
+                if not self._cv_wino_expand(view(t1, red), B, h, w, L[1], st, view(t2, red), L[2], view(out, cout), res):
+                    self._cv(view(t1, red), B, h, w, L[1], st, view(t2, red), act=self.act_bb)
+                    self._cv(view(t2, red), B, ho, wo, L[2], 1, view(out, cout), act=self.act_bb, res1=res)
             else:
                 t1 = buf(f"s{s}_t1", B, ho, wo, cout)
                 self._cv(view(cur, c), B, h, w, L[0], st, view(t1, cout), act=self.act_bb)

@@ -288,6 +288,57 @@ def wino_plan(desc, wm: int, plane_stride: int | None = None, work_elems: int | 
     return out
 
 
+def pack_expand_frag_host(planes, cout: int, k: int) -> np.ndarray:
+    """The hi / mid / lo planes [3, Cout*K] of a 1×1 conv (split_bf16x3_host) → MFMA fragment order
+    [Cout/32, K/16, 3, 64, 8] (flat int16), element (nb, s, plane, lane, j) = planes[plane][32·nb + lane % 32]
+    [16·s + 8·(lane // 32) + j]: what sp_winograd_f43_expand's waves load, 1 KB per (n block, k16 step, plane).
+    Host numpy at weight-pack time."""
+    p = np.asarray(planes)
+    if p.shape != (3, cout * k) or cout % 32 or k % 16:
+        raise ValueError(f"expand fragments: planes {p.shape} are not [3, {cout}*{k}] with Cout % 32 == 0, K % 16 == 0")
+    p = p.reshape(3, cout // 32, 32, k // 16, 2, 8)  # plane, nb, r, s, h, j
+    return np.ascontiguousarray(p.transpose(1, 3, 0, 4, 2, 5)).reshape(-1)
+
+
+def pack_expand_frag(planes: torch.Tensor, cout: int, k: int) -> torch.Tensor:
+    """pack_expand_frag_host of (device) planes, uploaded to their device (tests / tools)."""
+    return torch.from_numpy(pack_expand_frag_host(planes.detach().cpu().numpy(), cout, k)).to(planes.device)
+
+
+def wino_expand_plan(d2, work_elems: int, de, has_frag: bool = True, min_pixels: int = 0) -> dict:
+    """What sp_winograd_f43_expand would run for conv2's descriptor d2 (in its Winograd form, wino_desc) and the
+    expand's descriptor de under this thread's overrides (sp_winograd_expand_plan: no device call): {"fused",
+    "tiles", "units", "expand": conv_plan's dict of the expand}. Raises with the entry point's message."""
+    from ._lib import SpConvPlanInfo, SpWinogradExpandPlanInfo, call
+
+    info = SpWinogradExpandPlanInfo()
+    call("sp_winograd_expand_plan", C.byref(d2), int(work_elems), C.byref(de), int(bool(has_frag)), int(min_pixels),
+         C.byref(info))
+    return {"fused": info.fused, "tiles": info.tiles, "units": info.units,
+            "expand": {f: getattr(info.expand, f) for f, _ in SpConvPlanInfo._fields_}}
+
+
+def wino_expand(stages, d2, work: torch.Tensor, de, hook_args, frag: torch.Tensor | None, min_pixels: int = 0):
+    """The output stage of conv2's F(4×4) Winograd form (stages = wino_desc(d2, ...): its input and gemm stages have
+    been launched) and the 1×1 expand de that reads conv2's output (conv_desc, with hook_args), as ONE fused launch
+    where sp_winograd_expand_plan says so (conv2's output rows are then not written), else as the two launches
+    they were. frag: the expand's planes in fragment order (pack_expand_frag). Returns whether it fused."""
+    if frag is not None and (frag.dtype != torch.int16 or not frag.is_cuda or not frag.is_contiguous()
+                             or frag.numel() != 3 * de.Cout * de.Cin):
+        raise ValueError("wino_expand: fragment planes must be a contiguous int16 CUDA tensor of 3*Cout*K elements")
+    fused = bool(wino_expand_plan(d2, work.numel(), de, frag is not None, min_pixels)["fused"])
+    if not fused:
+        wino_launch(stages, only="output")
+        conv_launch(de, hook_args)
+        return False
+    m, cout, k = de.N * de.Ho * de.Wo, de.Cout, de.Cin
+    nbytes = 4 * (36 * d2.N * ((d2.H + 3) // 4) * ((d2.W + 3) // 4) * k + m * cout * (1 + bool(de.res1))) + 2 * frag.numel()
+    _launch("conv", "sp_winograd_f43_expand",
+            (C.byref(d2), work.data_ptr(), work.numel(), C.byref(de), frag.data_ptr(), frag.numel(), int(min_pixels),
+             stream()), 2 * m * cout * k, nbytes, (m, cout, k, 1, 1, "x3", "epi:res" if de.res1 else "epi:bn"))
+    return True
+
+
 def linear(x: V, rows: int, k: int, wt: torch.Tensor, n: int, out: V, *, bias=None, act=None,
            res1: V | None = None, res2: V | None = None, a2: V | None = None, row_scale=None,
            scale=None, workspace=None, wt16=None, wt_planes=None, ln=None, counters=None):

@@ -442,8 +442,12 @@ int sp_postprocess(const float* logits, const float* boxes, const int32_t* targe
 /*
  * JPEG decode (ABI v11): the step in front of A1 — serve.py:96-97 `Image.open(BytesIO(...)).convert("RGB")`,
  * which Pillow runs through libjpeg-turbo (ISLOW integer IDCT, fancy upsampling, integer YCbCr→RGB).
- * Split as the hardware wants it: the Huffman entropy decode (a serial bit stream) on the host, everything
- * per pixel on the GPU. Supported: 8-bit baseline / extended / progressive Huffman JPEGs with 1 (gray) or 3
+ * Split per file kind. Progressive, multi-scan and every other form: the Huffman entropy decode (a serial bit
+ * stream) on the host (sp_jpeg_decode_coefs), everything per pixel on the GPU (sp_jpeg_to_rgb). Baseline / extended
+ * sequential files with one interleaved scan (what cameras and Pillow's default save write) may instead leave the
+ * host after header parsing and one pass that removes the 0xFF00 stuffing: sp_jpeg_entropy_pack builds a scan
+ * package, sp_jpeg_entropy_decode turns it into the same coefficient array on the GPU (opt-in, below).
+ * Supported: 8-bit baseline / extended / progressive Huffman JPEGs with 1 (gray) or 3
  * (YCbCr, or RGB per the Adobe / component-id rules of libjpeg) components, luma at the maximum sampling
  * factors and chroma at 1x or 2x below it in each direction, restart intervals. Anything else returns
  * SP_JPEG_UNSUPPORTED (the caller keeps the reference's host decode for that image).
@@ -475,6 +479,55 @@ int sp_jpeg_decode_coefs(const uint8_t* data, int64_t len, sp_jpeg_layout* lay, 
  * agree (only corrupt or crafted coefficient data does): the caller then keeps Pillow's decode (ABI v12). */
 int sp_jpeg_to_rgb(const int16_t* coefs, const sp_jpeg_layout* lay, uint8_t* work, int64_t work_bytes, uint8_t* rgb,
                    int64_t rgb_stride, int32_t* status, void* stream);
+
+/*
+ * GPU entropy decode of baseline Huffman scans (added under ABI v20; spotter_amd/csrc/jpeg_entropy.hip): the
+ * self-synchronising parallel Huffman decode. The scan package is one byte buffer (pinned host memory, then its
+ * device copy): [6 Huffman tables: DC / AC per component, the host decoder's lookup form][nseg + 1 restart
+ * segment entries {int64 bit offset, int32 first MCU, int32 first subsequence}][the entropy-coded bytes of all
+ * segments with the 0xFF00 stuffing and the RSTn markers removed, each segment byte-aligned, zero padded].
+ */
+#define SP_JPEG_NOT_ELIGIBLE 1 /* not an error: the file keeps the host entropy decode */
+#define SP_JPEG_PKG_SMALL 2    /* pkg_cap < scan->pkg_bytes: call again with a buffer of that size */
+typedef struct {
+  int32_t ncomp, bpm;             /* components; blocks per MCU (<= 10) */
+  int32_t mcux, mcuy;             /* MCU grid */
+  int32_t restart_interval;       /* MCUs per restart segment, 0: one segment */
+  int32_t sub_bits;               /* subsequence size in bits */
+  int32_t slot_comp[10];          /* component of each block slot of an MCU, in scan order */
+  int32_t slot_v[10], slot_h[10]; /* the slot's block row / column inside its component's part of the MCU */
+  int64_t nmcu, nseg, nsub;       /* MCUs, restart segments, subsequences (one thread each) */
+  int64_t tab_off, seg_off, stream_off; /* byte offsets inside the package */
+  int64_t stream_bits;            /* entropy-coded bits (whole bytes) */
+  int64_t stream_bytes;           /* padded bytes of the stream area (a multiple of 16, >= 16 past the data) */
+  int64_t pkg_bytes;              /* bytes of the package to upload */
+  int64_t work_bytes;             /* device workspace sp_jpeg_entropy_decode needs */
+} sp_jpeg_scan;
+/* Host: parse data[0:len) with sp_jpeg_decode_coefs's parser and every one of its rejection rules, fill *lay as
+ * sp_jpeg_decode_coefs(.., NULL, 0) does (plus the latched quantisation tables once the package is written) and,
+ * for an eligible file (SOF0 / SOF1, 8-bit, Huffman, exactly one scan that holds all components, at most 10
+ * blocks per MCU, restart markers regular: the expected numbers, only 0xFF fill bytes before them), write the scan
+ * package into pkg[0:scan->pkg_bytes). Returns 0, SP_JPEG_NOT_ELIGIBLE (progressive, multi-scan, irregular
+ * restarts: *lay is filled, keep the host path), SP_JPEG_PKG_SMALL (scan->pkg_bytes holds the size to bring),
+ * SP_JPEG_UNSUPPORTED (as the host decoder), or -1. No device call. */
+int sp_jpeg_entropy_pack(const uint8_t* data, int64_t len, sp_jpeg_layout* lay, sp_jpeg_scan* scan, uint8_t* pkg,
+                         int64_t pkg_cap);
+/* Device: the uploaded package → coefs (device int16 [total_blocks][64], natural order, the array
+ * sp_jpeg_decode_coefs writes; coef_elems >= total_blocks * 64). work: scan->work_bytes device bytes, 16-byte
+ * aligned as pkg is. Allocates nothing; every kernel runs on `stream`. *status (device int32, zeroed by the caller,
+ * may be shared with sp_jpeg_to_rgb) gets reason bits ORed in when the result must be discarded: 2 a subsequence
+ * still unsynchronised after the round budget, 4 an invalid code or coefficient index, 8 bits consumed past a
+ * segment's end, 16 a block count that is not MCUs x blocks per MCU, 32 a DC prediction outside int32, 64 a
+ * segment that does not end at a block boundary (data after its last block). The caller
+ * then runs the file through sp_jpeg_decode_coefs, which accepts or refuses it by the host rules. */
+int sp_jpeg_entropy_decode(const uint8_t* pkg, const sp_jpeg_scan* scan, const sp_jpeg_layout* lay, uint8_t* work,
+                           int64_t work_bytes, int16_t* coefs, int64_t coef_elems, int32_t* status, void* stream);
+/* Host: sp_jpeg_entropy_decode's passes in the kernels' order on the CPU, over the same per-subsequence code
+ * (csrc/jpeg_entropy_core.h), for tests without a GPU. pkg and coefs are host memory; *status as above;
+ * rounds[0] = cross-workgroup launches in which a state still changed, rounds[1] = the most in-workgroup rounds
+ * any workgroup ran (rounds may be NULL). */
+int sp_jpeg_entropy_emulate(const uint8_t* pkg, const sp_jpeg_scan* scan, const sp_jpeg_layout* lay, int16_t* coefs,
+                            int64_t coef_elems, int32_t* status, int32_t* rounds);
 
 /*
  * JPEG encode (ABI v12): serve.py:139-142 `image.save(buffer, format="JPEG")`, which Pillow runs through

@@ -84,6 +84,15 @@ class SpJpegLayout(C.Structure):
     ]
 
 
+class SpJpegScan(C.Structure):
+    _fields_ = [
+        ("ncomp", i32), ("bpm", i32), ("mcux", i32), ("mcuy", i32), ("restart_interval", i32), ("sub_bits", i32),
+        ("slot_comp", i32 * 10), ("slot_v", i32 * 10), ("slot_h", i32 * 10),
+        ("nmcu", i64), ("nseg", i64), ("nsub", i64), ("tab_off", i64), ("seg_off", i64), ("stream_off", i64),
+        ("stream_bits", i64), ("stream_bytes", i64), ("pkg_bytes", i64), ("work_bytes", i64),
+    ]
+
+
 class SpJpegEncLayout(C.Structure):
     _fields_ = [
         ("width", i32), ("height", i32), ("quality", i32), ("h0", i32), ("v0", i32),
@@ -127,6 +136,7 @@ class SpCopySegmentsDesc(C.Structure):
 SP_DRAW_FILL, SP_DRAW_BLEND = 0, 1  # sp_draw_kind
 SP_DRAW_TILE_W, SP_DRAW_TILE_H = 64, 8
 SP_JPEG_UNSUPPORTED = -10
+SP_JPEG_NOT_ELIGIBLE, SP_JPEG_PKG_SMALL = 1, 2  # sp_jpeg_entropy_pack's non-error returns
 SP_BUILD_FUSED_LN = 1  # sp_build_flags bits (include/spotter_hip.h)
 SP_BUILD_BOUNDS = 2
 
@@ -183,6 +193,9 @@ _SIGS = {
     "sp_postprocess": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp]),
     "sp_jpeg_decode_coefs": (i32, [vp, i64, C.POINTER(SpJpegLayout), vp, i64]),
     "sp_jpeg_to_rgb": (i32, [vp, C.POINTER(SpJpegLayout), vp, i64, vp, i64, vp, vp]),
+    "sp_jpeg_entropy_pack": (i32, [vp, i64, C.POINTER(SpJpegLayout), C.POINTER(SpJpegScan), vp, i64]),
+    "sp_jpeg_entropy_decode": (i32, [vp, C.POINTER(SpJpegScan), C.POINTER(SpJpegLayout), vp, i64, vp, i64, vp, vp]),
+    "sp_jpeg_entropy_emulate": (i32, [vp, C.POINTER(SpJpegScan), C.POINTER(SpJpegLayout), vp, i64, vp, vp]),
     "sp_jpeg_enc_plan": (i32, [i32, i32, i32, i32, C.POINTER(SpJpegEncLayout)]),
     "sp_jpeg_enc_rgb": (i32, [vp, i64, i32, C.POINTER(SpJpegEncLayout), vp, i64, vp, i64, vp, vp]),
     "sp_jpeg_enc_max_bytes": (i64, [C.POINTER(SpJpegEncLayout), i64, i64]),

@@ -160,3 +160,28 @@ def batch_invariant_from_env(environ=None):
     if not (txt.isascii() and txt.isdigit()):
         raise ValueError(f"{BATCH_INVARIANT_ENV}={raw!r} must be off, 0 or an integer >= 1")
     return check_batch_invariant(int(txt))
+
+
+JPEG_ENTROPY_ENV = "SPOTTER_JPEG_ENTROPY"
+# where the Huffman entropy decode of baseline JPEGs runs (spotter_amd/jpeg.py JpegDecoder): "host" (the default),
+# "gpu", or "auto" (today the same as "gpu"; reserved so that a later change of the default needs no API change)
+JPEG_ENTROPY_MODES = ("host", "gpu", "auto")
+
+
+def check_jpeg_entropy(value: str) -> str:
+    """A JPEG_ENTROPY_MODES member, else ValueError naming the accepted values (and the env variable)."""
+    if value not in JPEG_ENTROPY_MODES:
+        raise ValueError(f"JPEG entropy mode {value!r} (e.g. from {JPEG_ENTROPY_ENV}) must be one of "
+                         f"{list(JPEG_ENTROPY_MODES)}")
+    return value
+
+
+def jpeg_entropy_from_env(environ=None) -> str:
+    """SPOTTER_JPEG_ENTROPY: unset or empty = "host"; "host", "gpu" or "auto" (case and surrounding blanks ignored);
+    anything else raises ValueError (at import of the drop-in serve.py, like a bad SPOTTER_PRECISION)."""
+    import os
+
+    raw = (os.environ if environ is None else environ).get(JPEG_ENTROPY_ENV)
+    if raw is None or not raw.strip():
+        return "host"
+    return check_jpeg_entropy(raw.strip().lower())

@@ -1,5 +1,6 @@
 // JPEG decode in front of A1 (serve.py:96-97: Image.open(BytesIO(..)).convert("RGB"), which Pillow runs
-// through libjpeg-turbo). The entropy decode is a serial bit stream and stays on the host (C++ below); the
+// through libjpeg-turbo). The entropy decode is a serial bit stream and stays on the host (C++ below; baseline
+// files may opt into the parallel decode of jpeg_entropy.hip, which writes the same coefficient array); the
 // per-pixel work runs on the GPU: dequantisation + the ISLOW integer IDCT per 8x8 block (jidctint.c), then
 // "fancy" triangle upsampling of the chroma planes (jdsample.c h2v1 / h2v2 / h1v2_fancy_upsample) with the
 // edge-row replication of the main controller's context rows (jdmainct.c), then the integer YCbCr→RGB

@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "../../include/spotter_hip.h"
+#include "jpeg_entropy_core.h"
 
 // libjpeg(-turbo)'s JPEG_MAX_DIMENSION (jmorecfg.h): larger frames raise JERR_IMAGE_TOO_BIG on load and save
 #define SP_JPEG_MAX_DIMENSION 65500
@@ -336,6 +337,12 @@ struct Decoder {
   bool corrupt = false;   // a condition libjpeg warns about or resynchronises from (see the header comment)
   int coef_bits[3][64];   // jdphuff.c coef_bits: successive-approximation state per coefficient (-1 = none)
   int scans_seen[3] = {0, 0, 0};
+  // scan package mode (sp_jpeg_entropy_pack): the scans are not decoded; the first one is packed for the GPU
+  // entropy decoder (pack_scan below) when the file is eligible
+  sp_jpeg_scan* pk = nullptr;
+  uint8_t* pkg = nullptr;
+  int64_t pkg_cap = 0;
+  int pk_scans = 0;
 
   int fail(int code, const char* msg) {
     set_error("sp_jpeg_decode_coefs: %s", msg);
@@ -562,6 +569,7 @@ struct Decoder {
     }
     Bits b{after, data + len};
     ScanCtx S{ns, {ci[0], ci[1], ci[2]}, {td[0], td[1], td[2]}, {ta[0], ta[1], ta[2]}, Ss, Se, Ah, Al};
+    if (pk) return pack_scan(S, after, next);
     if (!prog) scan_blocks<kBase>(S, b);
     else if (Ss == 0 && Ah == 0) scan_blocks<kDcFirst>(S, b);
     else if (Ss == 0) scan_blocks<kDcRefine>(S, b);
@@ -575,6 +583,121 @@ struct Decoder {
       ++r;
     }
     *next = r;
+    return 0;
+  }
+
+  // The scan package of an eligible file (include/spotter_hip.h sp_jpeg_scan): one pass over the scan bytes that
+  // drops the 0xFF00 stuffing and the RSTn markers, with Bits::restart's rules on them (the expected number, only
+  // 0xFF fill bytes before a marker); anything irregular is SP_JPEG_NOT_ELIGIBLE, so the host decoder decides.
+  int pack_scan(const ScanCtx& S, const uint8_t* after, const uint8_t** next) {
+    namespace je = jpeg_entropy;
+    sp_jpeg_scan& sc = *pk;
+    if (lay->progressive || S.ns != nc || pk_scans++ > 0) return SP_JPEG_NOT_ELIGIBLE;
+    memset(&sc, 0, sizeof(sc));
+    int bpm = 0;
+    for (int si = 0; si < S.ns; ++si) {
+      const int c = S.ci[si];
+      for (int v = 0; v < comp[c].v; ++v)
+        for (int h = 0; h < comp[c].h; ++h) {
+          if (bpm >= je::kMaxSlots) return SP_JPEG_NOT_ELIGIBLE;
+          sc.slot_comp[bpm] = c;
+          sc.slot_v[bpm] = v;
+          sc.slot_h[bpm] = h;
+          ++bpm;
+        }
+    }
+    const uint8_t* end = data + len;
+    const int64_t avail = end - after;
+    const int64_t nmcu = (int64_t)mcux * mcuy, ri = restart_interval;
+    const int64_t nseg = ri ? (nmcu + ri - 1) / ri : 1;
+    if (nseg - 1 > avail / 2) return SP_JPEG_NOT_ELIGIBLE;  // fewer bytes than the RSTn markers alone need
+    sc.ncomp = nc;
+    sc.bpm = bpm;
+    sc.mcux = mcux;
+    sc.mcuy = mcuy;
+    sc.restart_interval = restart_interval;
+    sc.sub_bits = je::kSubBits;
+    sc.nmcu = nmcu;
+    sc.nseg = nseg;
+    sc.tab_off = 0;
+    sc.seg_off = 6 * (int64_t)sizeof(je::DevHuff);
+    sc.stream_off = sc.seg_off + (nseg + 1) * (int64_t)sizeof(je::SegEnt);
+    je::Geom G;
+    G.ri = restart_interval;
+    G.nmcu = nmcu;
+    const int64_t nchunk = je::dc_nseg(G) * je::dc_chunks_per_seg(G);
+    sc.pkg_bytes = sc.stream_off + (avail + 15) / 16 * 16 + 16;
+    sc.nsub = avail * 8 / je::kSubBits + nseg + 1;
+    sc.work_bytes = je::work_layout(sc.nsub, nchunk).bytes;
+    if (!pkg || pkg_cap < sc.pkg_bytes) return SP_JPEG_PKG_SMALL;
+    memset(pkg, 0, (size_t)sc.seg_off);
+    je::DevHuff* tabs = reinterpret_cast<je::DevHuff*>(pkg);
+    for (int si = 0; si < S.ns; ++si)
+      for (int t = 0; t < 2; ++t) {
+        const Huff& h = t ? ac[S.ta[si]] : dc[S.td[si]];
+        je::DevHuff& d = tabs[2 * S.ci[si] + t];
+        memcpy(d.look, h.look, sizeof(d.look));
+        memcpy(d.maxcode, h.maxcode, sizeof(d.maxcode));
+        memcpy(d.valoff, h.valoff, sizeof(d.valoff));
+        memcpy(d.vals, h.vals, sizeof(d.vals));
+        d.maxcode[0] = d.valoff[0] = d.valoff[17] = 0;  // never read: build_huff leaves them unset
+        for (int l = 1; l <= 16; ++l)
+          if (d.maxcode[l] < 0) d.valoff[l] = 0;
+      }
+    je::SegEnt* segs = reinterpret_cast<je::SegEnt*>(pkg + sc.seg_off);
+    uint8_t* out = pkg + sc.stream_off;
+    int64_t o = 0, seg = 0, nsub = 0;
+    auto close_seg = [&]() {
+      const int64_t bits = o * 8 - segs[seg].bit;
+      const int64_t n = (bits + je::kSubBits - 1) / je::kSubBits;
+      nsub += n > 0 ? n : 1;
+    };
+    segs[0] = je::SegEnt{0, 0, 0};
+    const uint8_t* p = after;
+    for (;;) {
+      const uint8_t* ff = p < end ? static_cast<const uint8_t*>(memchr(p, 0xFF, (size_t)(end - p))) : nullptr;
+      const uint8_t* stop = ff ? ff : end;
+      memcpy(out + o, p, (size_t)(stop - p));
+      o += stop - p;
+      p = stop;
+      if (!ff || p + 1 >= end) {  // the data runs out with no marker: run() refuses the file (no EOI)
+        p = end;
+        break;
+      }
+      if (p[1] == 0x00) {
+        out[o++] = 0xFF;
+        p += 2;
+        continue;
+      }
+      const uint8_t* q = p;
+      while (q + 1 < end && q[1] == 0xFF) ++q;  // fill bytes
+      if (q + 1 >= end) {
+        p = end;
+        break;
+      }
+      const int m = q[1];
+      if (m == 0x00) return SP_JPEG_NOT_ELIGIBLE;  // FF FF 00: the host reader stops there as at a marker
+      if (m >= 0xD0 && m <= 0xD7) {
+        if (!ri || seg + 1 >= nseg || m != 0xD0 + (int)(seg & 7)) return SP_JPEG_NOT_ELIGIBLE;
+        close_seg();
+        ++seg;
+        segs[seg] = je::SegEnt{o * 8, (int32_t)(seg * ri), (int32_t)nsub};
+        p = q + 2;
+        continue;
+      }
+      p = q;  // the marker that ends the scan
+      break;
+    }
+    if (seg + 1 != nseg) return SP_JPEG_NOT_ELIGIBLE;  // restart markers missing
+    close_seg();
+    segs[nseg] = je::SegEnt{o * 8, (int32_t)nmcu, (int32_t)nsub};
+    sc.nsub = nsub;
+    sc.stream_bits = o * 8;
+    sc.stream_bytes = (o + 15) / 16 * 16 + 16;
+    memset(out + o, 0, (size_t)(sc.stream_bytes - o));
+    sc.pkg_bytes = sc.stream_off + sc.stream_bytes;
+    sc.work_bytes = je::work_layout(nsub, nchunk).bytes;
+    *next = p;
     return 0;
   }
 
@@ -633,7 +756,7 @@ struct Decoder {
         if (!decode) break;
         if (!zeroed) {
           if (!frame) return bad("SOS before SOF");
-          memset(coefs, 0, (size_t)lay->total_blocks * 64 * sizeof(int16_t));
+          if (coefs) memset(coefs, 0, (size_t)lay->total_blocks * 64 * sizeof(int16_t));
           zeroed = true;
         }
         const uint8_t* nx = nullptr;

@@ -9,6 +9,11 @@ Pillow's libjpeg-turbo, bit for bit (tests/test_jpeg.py, tests/test_gpu_kernels.
 needs) that also carries its device copy, which SpotterImageProcessor then uses instead of uploading it
 again. JPEG forms the library does not decode (CMYK, 12-bit, arithmetic coding, ...) and other image formats
 keep the reference's host decode: UnsupportedJpeg is raised and open_image falls back to Pillow's Image.open for that image.
+
+Opt-in (`JpegDecoder(device, entropy="gpu")`, or SPOTTER_JPEG_ENTROPY=gpu for the decoders open_image / image_module
+create): baseline files with one interleaved scan are entropy-decoded on the GPU too (sp_jpeg_entropy_pack on the
+host, sp_jpeg_entropy_decode on the device); every other file, and every file whose GPU status
+word is non-zero, takes the host entropy decode, so the pixels and the exceptions are the same in both modes.
 """
 from __future__ import annotations
 
@@ -19,7 +24,9 @@ import types
 import numpy as np
 import torch
 
-from ._lib import SP_JPEG_UNSUPPORTED, SpJpegEncLayout, SpJpegLayout, lib
+from ._lib import (SP_JPEG_NOT_ELIGIBLE, SP_JPEG_PKG_SMALL, SP_JPEG_UNSUPPORTED, SpJpegEncLayout, SpJpegLayout,
+                   SpJpegScan, lib)
+from .config import check_jpeg_entropy, jpeg_entropy_from_env
 
 
 JPEG_MAX_DIMENSION = 65500  # libjpeg's jmorecfg.h limit (csrc/jpeg_host.h SP_JPEG_MAX_DIMENSION)
@@ -44,6 +51,7 @@ def _check_pixels(lay) -> None:
 # decode buffers a JpegDecoder keeps between calls; a larger image gets buffers of its own for that call only
 KEEP_COEFS = 1 << 25  # int16 coefficients (64 MiB pinned + 64 MiB device): a 4K 4:4:4 frame fits
 KEEP_WORK = 1 << 26   # bytes of component planes
+KEEP_PKG = 1 << 26    # bytes of scan package (pinned + device) and of entropy workspace, entropy="gpu"
 
 
 def _buf(data):
@@ -78,6 +86,46 @@ def decode_coefs(data, out: np.ndarray | None = None):
     return lay, out[:need].reshape(-1, 64)
 
 
+def pack_scan(data):
+    """Host half of entropy="gpu": (layout, scan, package bytes as a uint8 array), or None for a file that is not
+    eligible (progressive, multi-scan, irregular restarts: it keeps the host entropy decode). Raises
+    UnsupportedJpeg where the host parser refuses the file. No device call."""
+    ptr, n, keep = _buf(data)
+    lay, scan = SpJpegLayout(), SpJpegScan()
+    L = lib()
+    rc = L.sp_jpeg_entropy_pack(ptr, n, C.byref(lay), C.byref(scan), None, 0)
+    pkg = None
+    if rc == SP_JPEG_PKG_SMALL:
+        _check_pixels(lay)
+        pkg = np.zeros(scan.pkg_bytes, dtype=np.uint8)
+        rc = L.sp_jpeg_entropy_pack(ptr, n, C.byref(lay), C.byref(scan), pkg.ctypes.data, pkg.size)
+    del keep
+    if rc == SP_JPEG_UNSUPPORTED:
+        raise UnsupportedJpeg(L.sp_last_error().decode(errors="replace"))
+    if rc == SP_JPEG_NOT_ELIGIBLE:
+        return None
+    if rc:
+        raise RuntimeError(f"sp_jpeg_entropy_pack: {L.sp_last_error().decode(errors='replace')}")
+    return lay, scan, pkg[:scan.pkg_bytes]
+
+
+def emulate_entropy(data):
+    """The GPU entropy decode's passes run on the CPU in the kernels' order (sp_jpeg_entropy_emulate): (layout,
+    int16 coefficients [total_blocks, 64], status word, (cross-workgroup launches in which an exit state still
+    changed, most in-workgroup rounds)), or None for a file that is not eligible."""
+    packed = pack_scan(data)
+    if packed is None:
+        return None
+    lay, scan, pkg = packed
+    co = np.empty(lay.total_blocks * 64, dtype=np.int16)
+    status, rounds = C.c_int32(0), (C.c_int32 * 2)()
+    L = lib()
+    if L.sp_jpeg_entropy_emulate(pkg.ctypes.data, C.byref(scan), C.byref(lay), co.ctypes.data, co.size,
+                                 C.byref(status), rounds):
+        raise RuntimeError(f"sp_jpeg_entropy_emulate: {L.sp_last_error().decode(errors='replace')}")
+    return lay, co.reshape(-1, 64), status.value, (rounds[0], rounds[1])
+
+
 def layout_dict(lay: SpJpegLayout) -> dict:
     d = {k: getattr(lay, k) for k in ("width", "height", "ncomp", "color", "progressive", "max_h", "max_v",
                                       "total_blocks", "plane_bytes")}
@@ -90,10 +138,20 @@ def layout_dict(lay: SpJpegLayout) -> dict:
 class JpegDecoder:
     """Per-device decoder state: a pinned host coefficient buffer and device buffers, grown as needed up to
     KEEP_COEFS / KEEP_WORK and reused (one decode at a time per decoder; the lock serialises concurrent
-    callers). A larger image decodes through buffers allocated for that call and released after it."""
+    callers). A larger image decodes through buffers allocated for that call and released after it.
 
-    def __init__(self, device):
+    entropy: where the Huffman decode of baseline files runs. "host" (default): sp_jpeg_decode_coefs, the
+    coefficients go up. "gpu" / "auto": the host only parses the headers and packs the scan (sp_jpeg_entropy_pack,
+    one pass that drops the 0xFF00 stuffing); the package goes up and sp_jpeg_entropy_decode writes the coefficients
+    on the device. Files that are not eligible (progressive, multi-scan, irregular restarts) and files whose GPU
+    status word comes back non-zero take the host path, so every file gives the host path's pixels or exception.
+    `stats` counts the paths: "gpu", "host" (not eligible), "fallback" {status word: count}, "h2d_bytes"."""
+
+    def __init__(self, device, entropy="host"):
         self.dev = torch.device(device)
+        self.entropy = check_jpeg_entropy(entropy)
+        self.stats = {"gpu": 0, "host": 0, "fallback": {}, "h2d_bytes": 0}
+        self._g: dict = {}  # entropy="gpu" buffers: pinned "pkg_host", device "pkg", "ent", "coefs", "work"
         self._lock = threading.Lock()
         self._host = None  # pinned int16
         self._coefs = None  # device int16
@@ -132,6 +190,10 @@ class JpegDecoder:
         lay = SpJpegLayout()
         L = lib()
         with self._lock:
+            if self.entropy != "host":
+                got = self._decode_gpu_entropy(L, ptr, n, out)
+                if got is not None:
+                    return got
             rc = L.sp_jpeg_decode_coefs(ptr, n, C.byref(lay), None, 0)
             if rc == SP_JPEG_UNSUPPORTED:
                 raise UnsupportedJpeg(L.sp_last_error().decode(errors="replace"))
@@ -174,9 +236,91 @@ class JpegDecoder:
                                       "code (corrupt or crafted data): left to Pillow")
             return out
 
+    def _decode_gpu_entropy(self, L, ptr, n, out):
+        """entropy="gpu": pack on the host into the reused pinned buffer, copy the package asynchronously, run the
+        entropy kernels and sp_jpeg_to_rgb, one status readback. The image, or None when the file takes the host path
+        (not eligible, or a non-zero status word); raises UnsupportedJpeg as the host parser does. Lock held."""
+        lay, scan = SpJpegLayout(), SpJpegScan()
+        g = self._g
+        if self._copied is not None:
+            self._copied.synchronize()  # the pinned package buffer is free again
+        host = g.get("pkg_host")
+        rc = L.sp_jpeg_entropy_pack(ptr, n, C.byref(lay), C.byref(scan), host.data_ptr() if host is not None else None,
+                                    host.numel() if host is not None else 0)
+        kept = True
+        if rc == SP_JPEG_PKG_SMALL:
+            _check_pixels(lay)
+            if scan.pkg_bytes > KEEP_PKG:
+                kept, host = False, torch.empty(scan.pkg_bytes, dtype=torch.uint8, pin_memory=True)
+            else:
+                _grow_kept(g, "pkg_host", scan.pkg_bytes, KEEP_PKG, dtype=torch.uint8, pin_memory=True)
+                host = g["pkg_host"]
+            rc = L.sp_jpeg_entropy_pack(ptr, n, C.byref(lay), C.byref(scan), host.data_ptr(), host.numel())
+        if rc == SP_JPEG_UNSUPPORTED:
+            raise UnsupportedJpeg(L.sp_last_error().decode(errors="replace"))
+        if rc == SP_JPEG_NOT_ELIGIBLE:
+            self.stats["host"] += 1
+            return None
+        if rc:
+            raise RuntimeError(f"sp_jpeg_entropy_pack: {L.sp_last_error().decode(errors='replace')}")
+        _check_pixels(lay)
+        ncoef = lay.total_blocks * 64
+        need = {"pkg": (scan.pkg_bytes, KEEP_PKG, torch.uint8), "ent": (scan.work_bytes, KEEP_PKG, torch.uint8),
+                "coefs": (ncoef, KEEP_COEFS, torch.int16), "work": (lay.plane_bytes, KEEP_WORK, torch.uint8)}
+        if any(sz > cap for sz, cap, _ in need.values()):
+            kept = False
+        if kept:
+            if any(g.get(k) is None or g[k].numel() < sz for k, (sz, _, _) in need.items()) and self._done is not None:
+                self._done.synchronize()  # the old buffers may still be read by the previous decode on another stream
+            for k, (sz, cap, dt) in need.items():
+                _grow_kept(g, k, sz, cap, dtype=dt, device=self.dev)
+            dev = {k: g[k] for k in need}
+        else:
+            dev = {k: torch.empty(max(sz, 16), dtype=dt, device=self.dev) for k, (sz, _, dt) in need.items()}
+        cur = torch.cuda.current_stream(self.dev)
+        if kept and self._done is not None:
+            cur.wait_event(self._done)  # another stream's previous decode may still read the buffers
+        dev["pkg"][:scan.pkg_bytes].copy_(host[:scan.pkg_bytes], non_blocking=True)
+        copied = torch.cuda.Event()
+        copied.record()
+        H, W = lay.height, lay.width
+        if out is None:
+            out = torch.empty((H, W, 3), dtype=torch.uint8, device=self.dev)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.shape == (H, W, 3) and out.is_contiguous()
+        self._status.zero_()
+        rc = L.sp_jpeg_entropy_decode(dev["pkg"].data_ptr(), C.byref(scan), C.byref(lay), dev["ent"].data_ptr(),
+                                      dev["ent"].numel(), dev["coefs"].data_ptr(), dev["coefs"].numel(),
+                                      self._status.data_ptr(), cur.cuda_stream)
+        if rc:
+            raise RuntimeError(f"sp_jpeg_entropy_decode: {L.sp_last_error().decode(errors='replace')}")
+        rc = L.sp_jpeg_to_rgb(dev["coefs"].data_ptr(), C.byref(lay), dev["work"].data_ptr(), dev["work"].numel(),
+                              out.data_ptr(), W * 3, self._status.data_ptr(), cur.cuda_stream)
+        if rc:
+            raise RuntimeError(f"sp_jpeg_to_rgb: {L.sp_last_error().decode(errors='replace')}")
+        self._status_host.copy_(self._status, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(cur)
+        done.synchronize()
+        if kept:
+            self._copied, self._done = copied, done
+        self.stats["h2d_bytes"] += int(scan.pkg_bytes)
+        st = int(self._status_host[0])
+        if st:  # the GPU result is discarded; the host path accepts the file or raises UnsupportedJpeg by its own rules
+            self.stats["fallback"][st] = self.stats["fallback"].get(st, 0) + 1
+            return None
+        self.stats["gpu"] += 1
+        return out
+
 
 _decoders: dict = {}
 _dec_lock = threading.Lock()
+
+
+def _grow_kept(store: dict, key, n, cap, **kw):
+    """store[key] grown to hold n elements (at least 1 MiB worth, at most cap)."""
+    t = store.get(key)
+    if t is None or t.numel() < n:
+        store[key] = torch.empty(min(cap, max(n, 1 << 20)), **kw)
 
 
 class _ArrowArray(C.Structure):
@@ -306,12 +450,26 @@ def encoder(device=None) -> JpegEncoder:
         return e
 
 
-def decoder(device=None) -> JpegDecoder:
+_env_entropy = None  # SPOTTER_JPEG_ENTROPY as open_image first found it (read and validated once per process)
+
+
+def default_entropy() -> str:
+    """The entropy mode of the decoders open_image creates: SPOTTER_JPEG_ENTROPY, read once."""
+    global _env_entropy
+    if _env_entropy is None:
+        _env_entropy = jpeg_entropy_from_env()
+    return _env_entropy
+
+
+def decoder(device=None, entropy="host") -> JpegDecoder:
+    """The shared decoder of a device and entropy mode (the environment is not read here)."""
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    mode = check_jpeg_entropy(entropy)
+    key = dev if mode == "host" else (dev, mode)
     with _dec_lock:
-        d = _decoders.get(dev)
+        d = _decoders.get(key)
         if d is None:
-            d = _decoders[dev] = JpegDecoder(dev)
+            d = _decoders[key] = JpegDecoder(dev, mode)
         return d
 
 
@@ -481,27 +639,29 @@ def _gpu_jpeg_options(im, fp, format, params):
     return q, _SUBSAMPLING[sub], comment
 
 
-def _device_image(im, data, device=None):
+def _device_image(im, data, device=None, entropy="host"):
     """A file Pillow has opened (its header parse, identification rules and decompression-bomb check have run,
     raising whatever the reference raises) → its GPU-decoded DeviceRGBImage, or None to keep Pillow's image:
     other formats and modes, MPO, and every JPEG the library leaves to the host decoder."""
     if type(im) is not _JpegPlugin.JpegImageFile or im.mode != "RGB":
         return None
     try:
-        return DeviceRGBImage(decoder(device).decode(data), info=im.info)
+        dec = decoder(device) if entropy == "host" else decoder(device, entropy)
+        return DeviceRGBImage(dec.decode(data), info=im.info)
     except UnsupportedJpeg:
         return None
 
 
-def open_image(data, device=None):
+def open_image(data, device=None, entropy=None):
     """serve.py:96's `Image.open(BytesIO(image_bytes))` for raw bytes: a DeviceRGBImage for the JPEGs the
     library decodes (pixels identical to Pillow's), Pillow's own image otherwise. Pillow parses the header
-    first, so a file Pillow refuses raises exactly what the reference raises."""
+    first, so a file Pillow refuses raises exactly what the reference raises. entropy: "host" / "gpu" / "auto",
+    None: SPOTTER_JPEG_ENTROPY as first read (default_entropy)."""
     import io
 
     b = bytes(data)
     im = _PILImage.open(io.BytesIO(b))
-    dev = _device_image(im, b, device)
+    dev = _device_image(im, b, device, default_entropy() if entropy is None else entropy)
     if dev is None:
         return im
     im.close()
@@ -516,6 +676,8 @@ class _ImageModule(types.ModuleType):
     def __init__(self, device=None):
         super().__init__("PIL.Image", _PILImage.__doc__)
         self._spotter_device = device
+        # latched here, once: a bad SPOTTER_JPEG_ENTROPY fails the drop-in's import, later changes are not seen
+        self._spotter_entropy = jpeg_entropy_from_env()
 
     def __getattr__(self, name):
         return getattr(_PILImage, name)
@@ -525,7 +687,7 @@ class _ImageModule(types.ModuleType):
 
         im = _PILImage.open(fp, mode, formats)
         if mode == "r" and isinstance(fp, io.BytesIO):
-            dev = _device_image(im, fp.getvalue(), self._spotter_device)
+            dev = _device_image(im, fp.getvalue(), self._spotter_device, self._spotter_entropy)
             if dev is not None:
                 im.close()
                 return dev

@@ -141,7 +141,7 @@ async def handle(body: bytes, client, proc, model, stamps, open_fn=None, jitter=
     return json.dumps({"amenities_description": desc, "images": results})
 
 
-def measure(preset="r101vd", iters=200, model=None, decode="gpu", jitter=False):
+def measure(preset="r101vd", iters=200, model=None, decode="gpu", jitter=False, image=None):
     import httpx
     import numpy as np
     import torch
@@ -149,7 +149,9 @@ def measure(preset="r101vd", iters=200, model=None, decode="gpu", jitter=False):
     from spotter_amd import SpotterForObjectDetection, SpotterImageProcessor
     from spotter_amd.config import PRESETS
 
-    with open(os.path.join(ROOT, "tests", "golden", "test_pic.jpg"), "rb") as f:
+    # image: another JPEG file to serve (e.g. a baseline re-encode of the fixture, which SPOTTER_JPEG_ENTROPY=gpu
+    # decodes entirely on the GPU; the fixture itself is progressive and keeps the host entropy decode)
+    with open(image or os.path.join(ROOT, "tests", "golden", "test_pic.jpg"), "rb") as f:
         jpeg = f.read()
     srv, url = serve_bytes(jpeg)
     model = model or SpotterForObjectDetection(PRESETS[preset], use_graphs=True)
@@ -174,12 +176,15 @@ def measure(preset="r101vd", iters=200, model=None, decode="gpu", jitter=False):
         srv.shutdown()
     torch.cuda.synchronize()
     total = np.array(total)
-    return {"metric": "p50 /detect latency, whole request (HTTP fetch from a local server, JPEG decode, "
-                      "preprocess, forward, post-process, labels, draw, JPEG re-encode, base64, response JSON), "
-                      "bs1, 1200x717 JPEG",
-            "p50_ms": round(float(np.percentile(total, 50)), 3), "p95_ms": round(float(np.percentile(total, 95)), 3),
-            "iters": iters, "preset": preset, "decode": decode, "box_jitter": bool(jitter),
-            "stages_p50_ms": {k: round(float(np.percentile(v, 50)), 3) for k, v in stamps.items()}}
+    res = {"metric": "p50 /detect latency, whole request (HTTP fetch from a local server, JPEG decode, "
+                     "preprocess, forward, post-process, labels, draw, JPEG re-encode, base64, response JSON), "
+                     "bs1, 1200x717 JPEG",
+           "p50_ms": round(float(np.percentile(total, 50)), 3), "p95_ms": round(float(np.percentile(total, 95)), 3),
+           "iters": iters, "preset": preset, "decode": decode, "box_jitter": bool(jitter),
+           "stages_p50_ms": {k: round(float(np.percentile(v, 50)), 3) for k, v in stamps.items()}}
+    if image:
+        res.update(image=os.path.basename(image), jpeg_entropy=os.environ.get("SPOTTER_JPEG_ENTROPY", "host"))
+    return res
 
 
 def main():
@@ -188,8 +193,9 @@ def main():
     ap.add_argument("--preset", default="r101vd")
     ap.add_argument("--decode", default="gpu", choices=["gpu", "host"])
     ap.add_argument("--jitter", action="store_true", help="draw each request's boxes at a random sub-pixel offset")
+    ap.add_argument("--image", default=None, help="JPEG file to serve instead of tests/golden/test_pic.jpg")
     a = ap.parse_args()
-    print(json.dumps(measure(a.preset, a.iters, decode=a.decode, jitter=a.jitter)))
+    print(json.dumps(measure(a.preset, a.iters, decode=a.decode, jitter=a.jitter, image=a.image)))
 
 
 if __name__ == "__main__":

@@ -481,6 +481,49 @@ int sp_jpeg_to_rgb(const int16_t* coefs, const sp_jpeg_layout* lay, uint8_t* wor
                    int64_t rgb_stride, int32_t* status, void* stream);
 
 /*
+ * Batched coefficients → RGB (added under ABI v20): sp_jpeg_to_rgb's two passes over up to SP_JPEG_BATCH_MAX
+ * images in two launches in all. The images share one coefficient buffer, one `work` buffer and one RGB arena;
+ * one table row per image says where its parts lie and which workgroups of each launch are its own. A workgroup
+ * never spans two images: it finds its row by a uniform binary search of the first-workgroup column.
+ */
+#define SP_JPEG_BATCH_MAX 64
+#define SP_JPEG_BATCH_IDCT_BLOCKS 32  /* 8x8 blocks per workgroup of the IDCT launch (as sp_jpeg_to_rgb) */
+#define SP_JPEG_BATCH_COLOR_PX 1024   /* pixels per workgroup of the colour launch (256 threads x 4 pixels) */
+typedef struct {
+  sp_jpeg_layout lay;
+  int64_t coef_off;        /* first int16 element of the image's coefficients in the shared buffer */
+  int64_t work_off;        /* byte offset of its planes in the shared `work`, a multiple of 16 */
+  int64_t rgb_off;         /* byte offset of its first RGB row in the arena; the plan gives multiples of 256 */
+  int64_t rgb_stride;      /* bytes between its RGB rows, >= 3 * width; the plan gives packed rows */
+  int32_t first_wg_idct;   /* its first workgroup in the IDCT launch: exclusive prefix sum of the counts */
+  int32_t first_wg_color;  /* the same for the colour launch */
+} sp_jpeg_batch_item;
+typedef struct {
+  int64_t coef_elems;      /* int16 elements of the shared coefficient buffer */
+  int64_t work_bytes;      /* bytes of the shared `work` */
+  int64_t rgb_bytes;       /* bytes of the RGB arena */
+  int64_t wg_idct;         /* workgroups of the IDCT launch: sum of ceil(total_blocks / 32) */
+  int64_t wg_color;        /* workgroups of the colour launch: sum of ceil(width * height / 1024) */
+} sp_jpeg_batch_totals;
+/* Host: lay out n images (their layouts as sp_jpeg_decode_coefs filled them) in the three shared buffers: fills
+ * items[i] (a copy of lays[i], the offsets, packed RGB rows, both prefix columns) and *totals. Each layout passes
+ * sp_jpeg_to_rgb's consistency checks and must be packed as the parser writes it (blocks and planes of the
+ * components in order, inside total_blocks / plane_bytes). Refused with -1 and a message: a NULL pointer, n outside
+ * [1, SP_JPEG_BATCH_MAX], an inconsistent layout, more than 2^31 - 1 workgroups in a launch. No device call. */
+int sp_jpeg_batch_plan(const sp_jpeg_layout* lays, int n, sp_jpeg_batch_item* items, sp_jpeg_batch_totals* totals);
+/* Device: exactly two launches for the whole batch. coefs / work / rgb are the shared device buffers (coefs 2-byte,
+ * work 16-byte, rgb 4-byte aligned); items_dev is the device copy of the table (8-byte aligned; it may travel in the
+ * same upload as the coefficients), items_host the same bytes on the host, read here only to check the arguments:
+ * every layout as sp_jpeg_batch_plan checks it, every range inside its buffer, the ranges of one buffer pairwise
+ * disjoint, strides >= 3 * width, both prefix columns and *totals what the layouts give. status: device int32 [n],
+ * zeroed by the caller; status[i] is set to 1 when image i leaves the IDCT envelope (see sp_jpeg_to_rgb) and is
+ * written by no other image. The arithmetic is sp_jpeg_to_rgb's own device code, so the pixels are the same.
+ * Asynchronous on `stream`; allocates nothing, copies nothing; can be captured in a graph. */
+int sp_jpeg_batch_to_rgb(const int16_t* coefs, int64_t coef_elems, const sp_jpeg_batch_item* items_dev,
+                         const sp_jpeg_batch_item* items_host, int n, const sp_jpeg_batch_totals* totals, uint8_t* work,
+                         int64_t work_bytes, uint8_t* rgb, int64_t rgb_bytes, int32_t* status, void* stream);
+
+/*
  * GPU entropy decode of baseline Huffman scans (added under ABI v20; spotter_amd/csrc/jpeg_entropy.hip): the
  * self-synchronising parallel Huffman decode. The scan package is one byte buffer (pinned host memory, then its
  * device copy): [6 Huffman tables: DC / AC per component, the host decoder's lookup form][nseg + 1 restart

@@ -84,6 +84,18 @@ class SpJpegLayout(C.Structure):
     ]
 
 
+SP_JPEG_BATCH_MAX, SP_JPEG_BATCH_IDCT_BLOCKS, SP_JPEG_BATCH_COLOR_PX = 64, 32, 1024
+
+
+class SpJpegBatchItem(C.Structure):
+    _fields_ = [("lay", SpJpegLayout), ("coef_off", i64), ("work_off", i64), ("rgb_off", i64), ("rgb_stride", i64),
+                ("first_wg_idct", i32), ("first_wg_color", i32)]
+
+
+class SpJpegBatchTotals(C.Structure):
+    _fields_ = [("coef_elems", i64), ("work_bytes", i64), ("rgb_bytes", i64), ("wg_idct", i64), ("wg_color", i64)]
+
+
 class SpJpegScan(C.Structure):
     _fields_ = [
         ("ncomp", i32), ("bpm", i32), ("mcux", i32), ("mcuy", i32), ("restart_interval", i32), ("sub_bits", i32),
@@ -193,6 +205,10 @@ _SIGS = {
     "sp_postprocess": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp]),
     "sp_jpeg_decode_coefs": (i32, [vp, i64, C.POINTER(SpJpegLayout), vp, i64]),
     "sp_jpeg_to_rgb": (i32, [vp, C.POINTER(SpJpegLayout), vp, i64, vp, i64, vp, vp]),
+    "sp_jpeg_batch_plan": (i32, [C.POINTER(SpJpegLayout), i32, C.POINTER(SpJpegBatchItem),
+                                 C.POINTER(SpJpegBatchTotals)]),
+    "sp_jpeg_batch_to_rgb": (i32, [vp, i64, vp, C.POINTER(SpJpegBatchItem), i32, C.POINTER(SpJpegBatchTotals), vp, i64,
+                                   vp, i64, vp, vp]),
     "sp_jpeg_entropy_pack": (i32, [vp, i64, C.POINTER(SpJpegLayout), C.POINTER(SpJpegScan), vp, i64]),
     "sp_jpeg_entropy_decode": (i32, [vp, C.POINTER(SpJpegScan), C.POINTER(SpJpegLayout), vp, i64, vp, i64, vp, vp]),
     "sp_jpeg_entropy_emulate": (i32, [vp, C.POINTER(SpJpegScan), C.POINTER(SpJpegLayout), vp, i64, vp, vp]),

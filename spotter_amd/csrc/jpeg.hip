@@ -4,7 +4,9 @@
 // per-pixel work runs on the GPU: dequantisation + the ISLOW integer IDCT per 8x8 block (jidctint.c), then
 // "fancy" triangle upsampling of the chroma planes (jdsample.c h2v1 / h2v2 / h1v2_fancy_upsample) with the
 // edge-row replication of the main controller's context rows (jdmainct.c), then the integer YCbCr→RGB
-// tables (jdcolor.c) — the same integer arithmetic, so the pixels are Pillow's, bit for bit.
+// tables (jdcolor.c) — the same integer arithmetic, so the pixels are Pillow's, bit for bit. Two forms share the
+// device code: one image per call (sp_jpeg_to_rgb, the layout in kernel arguments) and a batch of images in two
+// launches (sp_jpeg_batch_to_rgb, one table row per image in device memory).
 // libjpeg-turbo is a dependency of Pillow (absent from /root/reference); its published algorithms are
 // restated here and in oracle/jpeg_np.py, and tests/test_jpeg.py pins both against Pillow's own decode.
 #include <cstdint>
@@ -84,12 +86,14 @@ __device__ __forceinline__ uint8_t idct_limit(int64_t x) {
 // crafted data) sets *status, and the caller gives that file to Pillow.
 constexpr int64_t kEnv16 = (1 << 14) - 1;
 
-// 8 threads per 8x8 block (thread = column in pass 1, row in pass 2), 32 blocks per workgroup.
-__global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restrict__ coefs, const sp_jpeg_layout L,
-                                                        uint8_t* __restrict__ work, int32_t* __restrict__ status) {
+// 8 threads per 8x8 block (thread = column in pass 1, row in pass 2), 32 blocks per workgroup: workgroup `wg` of
+// one image's IDCT. Shared by the single-image kernel (L in the kernel arguments) and the batched one (L in the
+// device item table); called by all 256 threads of the workgroup.
+__device__ __forceinline__ void idct_workgroup(const int16_t* __restrict__ coefs, const sp_jpeg_layout& L,
+                                               uint8_t* __restrict__ work, int32_t* __restrict__ status, int64_t wg) {
   __shared__ int32_t ws[32][8][9];
   const int lb = threadIdx.x >> 3, t = threadIdx.x & 7;
-  const int64_t blk = (int64_t)blockIdx.x * 32 + lb;
+  const int64_t blk = wg * 32 + lb;
   const bool live = blk < L.total_blocks;
   int c = 0;
   if (L.ncomp > 1 && blk >= L.block_off[1]) c = 1;
@@ -134,6 +138,11 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restric
   *reinterpret_cast<uint2*>(dst) = make_uint2(w0, w1);
 }
 
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restrict__ coefs, const sp_jpeg_layout L,
+                                                        uint8_t* __restrict__ work, int32_t* __restrict__ status) {
+  idct_workgroup(coefs, L, work, status, blockIdx.x);
+}
+
 // One chroma sample at output (x, y): jdsample.c fancy upsampling (triangle filter 3/4 nearer + 1/4 further
 // in each upsampled direction), rows past the component's edge replicating its first / last row as the
 // main controller's context rows do; box replication where libjpeg-turbo picks it (downsampled width <= 2
@@ -166,20 +175,14 @@ __device__ __forceinline__ int chroma_at(const uint8_t* pl, int64_t stride, int 
 
 __device__ __forceinline__ uint8_t clamp8(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
-// One thread per output pixel: luma from its plane, chroma upsampled, jdcolor.c ycc_rgb_convert (SCALEBITS 16
-// fixed point: Cr→R 1.40200, Cb→B 1.77200, G = y + ((−0.34414·Cb + ½ − 0.71414·Cr) >> 16)).
-__global__ __launch_bounds__(256) void jpeg_color_kernel(const sp_jpeg_layout L, const uint8_t* __restrict__ work,
-                                                         uint8_t* __restrict__ rgb, int64_t rgb_stride) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (int64_t)L.width * L.height) return;
-  const int y = (int)(i / L.width), x = (int)(i - (int64_t)y * L.width);
-  uint8_t* o = rgb + (int64_t)y * rgb_stride + (int64_t)x * 3;
+// One output pixel (x, y): luma from its plane, chroma upsampled, jdcolor.c ycc_rgb_convert (SCALEBITS 16 fixed
+// point: Cr→R 1.40200, Cb→B 1.77200, G = y + ((−0.34414·Cb + ½ − 0.71414·Cr) >> 16)). Returns R | G << 8 | B << 16.
+// Shared by the single-image kernel and the batched one.
+__device__ __forceinline__ uint32_t color_pixel(const sp_jpeg_layout& L, const uint8_t* __restrict__ work, int x,
+                                                int y) {
   SP_BCHECK(L.plane_off[0] + (int64_t)y * L.bw[0] * 8 + x, L.ncomp > 1 ? L.plane_off[1] : L.plane_bytes);
   const int yy = work[L.plane_off[0] + (int64_t)y * L.bw[0] * 8 + x];
-  if (L.ncomp == 1) {
-    o[0] = o[1] = o[2] = (uint8_t)yy;
-    return;
-  }
+  if (L.ncomp == 1) return (uint32_t)yy * 0x010101u;
   int cc[2];
 #pragma unroll
   for (int k = 1; k < 3; ++k) {
@@ -192,19 +195,108 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const sp_jpeg_layout L,
     SP_BCHECK(L.plane_off[k] + ((int64_t)L.bh[k] * 8 - 1) * L.bw[k] * 8 + L.bw[k] * 8 - 1, k == 1 && L.ncomp > 2 ? L.plane_off[2] : L.plane_bytes);
     cc[k - 1] = chroma_at(work + L.plane_off[k], (int64_t)L.bw[k] * 8, rh, rv, dw, dh, x, y);
   }
-  if (L.color == 2) {  // RGB components: no conversion
-    o[0] = (uint8_t)yy;
-    o[1] = (uint8_t)cc[0];
-    o[2] = (uint8_t)cc[1];
-    return;
-  }
+  if (L.color == 2)  // RGB components: no conversion
+    return (uint32_t)yy | (uint32_t)cc[0] << 8 | (uint32_t)cc[1] << 16;
   const int cb = cc[0] - 128, cr = cc[1] - 128;
   const int r_off = (91881 * cr + 32768) >> 16;
   const int b_off = (116130 * cb + 32768) >> 16;
   const int g_off = (-22554 * cb + 32768 + -46802 * cr) >> 16;
-  o[0] = clamp8(yy + r_off);
-  o[1] = clamp8(yy + g_off);
-  o[2] = clamp8(yy + b_off);
+  return (uint32_t)clamp8(yy + r_off) | (uint32_t)clamp8(yy + g_off) << 8 | (uint32_t)clamp8(yy + b_off) << 16;
+}
+
+// One thread per output pixel.
+__global__ __launch_bounds__(256) void jpeg_color_kernel(const sp_jpeg_layout L, const uint8_t* __restrict__ work,
+                                                         uint8_t* __restrict__ rgb, int64_t rgb_stride) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)L.width * L.height) return;
+  const int y = (int)(i / L.width), x = (int)(i - (int64_t)y * L.width);
+  uint8_t* o = rgb + (int64_t)y * rgb_stride + (int64_t)x * 3;
+  const uint32_t p = color_pixel(L, work, x, y);
+  o[0] = (uint8_t)p;
+  o[1] = (uint8_t)(p >> 8);
+  o[2] = (uint8_t)(p >> 16);
+}
+
+// ------------------------------------------------------------------------------------------------ batched
+// The same two passes over a batch of images in one launch each: a workgroup serves one image, found by a uniform
+// binary search of the items' first-workgroup column (an exclusive prefix sum, strictly increasing: every image
+// has at least one block and one pixel), as sp_copy_segments finds its segment.
+__device__ __forceinline__ int batch_image(const sp_jpeg_batch_item* __restrict__ items, int n,
+                                           int32_t sp_jpeg_batch_item::*first, int wg) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (items[mid].*first <= wg) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void jpeg_idct_batch_kernel(const int16_t* __restrict__ coefs, int64_t coef_elems,
+                                                              const sp_jpeg_batch_item* __restrict__ items, int n,
+                                                              uint8_t* __restrict__ work, int64_t work_bytes,
+                                                              int32_t* __restrict__ status) {
+  const int img = batch_image(items, n, &sp_jpeg_batch_item::first_wg_idct, (int)blockIdx.x);
+  SP_BCHECK(img, n);
+  const sp_jpeg_batch_item& it = items[img];
+  const int64_t wg = (int64_t)blockIdx.x - it.first_wg_idct;
+  SP_BCHECK(wg, (it.lay.total_blocks + 31) / 32);
+  SP_BCHECK(it.coef_off + it.lay.total_blocks * 64 - 1, coef_elems);
+  SP_BCHECK(it.work_off + it.lay.plane_bytes - 1, work_bytes);
+  idct_workgroup(coefs + it.coef_off, it.lay, work + it.work_off, status + img, wg);
+}
+
+// 4 consecutive pixels (in row-major order over the image) per thread, SP_JPEG_BATCH_COLOR_PX per workgroup.
+// Where the rows are packed (rgb_stride == 3·width) the 4 pixels are 12 consecutive bytes at a multiple of 12
+// from the image's 256-byte aligned start, row ends included, and go out as three dword stores; strided rows
+// and the image's last, partial group go out bytewise.
+__global__ __launch_bounds__(256) void jpeg_color_batch_kernel(const sp_jpeg_batch_item* __restrict__ items, int n,
+                                                               const uint8_t* __restrict__ work, int64_t work_bytes,
+                                                               uint8_t* __restrict__ rgb, int64_t rgb_bytes) {
+  const int img = batch_image(items, n, &sp_jpeg_batch_item::first_wg_color, (int)blockIdx.x);
+  SP_BCHECK(img, n);
+  const sp_jpeg_batch_item& it = items[img];
+  const sp_jpeg_layout& L = it.lay;
+  const int64_t px = (int64_t)L.width * L.height;
+  const int64_t wg = (int64_t)blockIdx.x - it.first_wg_color;
+  SP_BCHECK(wg, (px + SP_JPEG_BATCH_COLOR_PX - 1) / SP_JPEG_BATCH_COLOR_PX);
+  SP_BCHECK(it.work_off + L.plane_bytes - 1, work_bytes);
+  const int64_t i0 = (wg * 256 + threadIdx.x) * 4;
+  if (i0 >= px) return;
+  const uint8_t* planes = work + it.work_off;
+  uint8_t* base = rgb + it.rgb_off;
+  uint32_t p[4] = {0, 0, 0, 0};
+  int y = (int)(i0 / L.width), x = (int)(i0 - (int64_t)y * L.width);
+  const int live = px - i0 < 4 ? (int)(px - i0) : 4;
+  const int y0 = y, x0 = x;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (k < live) p[k] = color_pixel(L, planes, x, y);
+    if (++x == L.width) {
+      x = 0;
+      ++y;
+    }
+  }
+  if (live == 4 && it.rgb_stride == 3LL * L.width) {
+    SP_BCHECK(it.rgb_off + i0 * 3 + 11, rgb_bytes);
+    uint32_t* o = reinterpret_cast<uint32_t*>(base + i0 * 3);
+    o[0] = p[0] | p[1] << 24;
+    o[1] = p[1] >> 8 | p[2] << 16;
+    o[2] = p[2] >> 16 | p[3] << 8;
+    return;
+  }
+  y = y0;
+  x = x0;
+  for (int k = 0; k < live; ++k) {
+    SP_BCHECK(it.rgb_off + (int64_t)y * it.rgb_stride + (int64_t)x * 3 + 2, rgb_bytes);
+    uint8_t* o = base + (int64_t)y * it.rgb_stride + (int64_t)x * 3;
+    o[0] = (uint8_t)p[k];
+    o[1] = (uint8_t)(p[k] >> 8);
+    o[2] = (uint8_t)(p[k] >> 16);
+    if (++x == L.width) {
+      x = 0;
+      ++y;
+    }
+  }
 }
 
 }  // namespace
@@ -227,14 +319,12 @@ extern "C" int sp_jpeg_to_rgb(const int16_t* coefs, const sp_jpeg_layout* lay, u
                               uint8_t* rgb, int64_t rgb_stride, int32_t* status, void* stream) {
   using namespace sp;
   SP_ARG_CHECK(coefs && lay && work && rgb, "sp_jpeg_to_rgb: null args");
-  SP_ARG_CHECK(lay->ncomp == 1 || lay->ncomp == 3, "sp_jpeg_to_rgb: ncomp %d", lay->ncomp);
+  if (int rc = check_layout(lay, "sp_jpeg_to_rgb")) return rc;
   SP_ARG_CHECK(work_bytes >= lay->plane_bytes, "sp_jpeg_to_rgb: work %lld < %lld bytes", (long long)work_bytes,
                (long long)lay->plane_bytes);
   SP_ARG_CHECK(rgb_stride >= 3LL * lay->width, "sp_jpeg_to_rgb: rgb_stride");
   for (int c = 0; c < lay->ncomp; ++c)
-    SP_ARG_CHECK((int64_t)lay->bw[c] * 8 >= ((int64_t)lay->width * lay->h[c] + lay->max_h - 1) / lay->max_h &&
-                     (int64_t)lay->bh[c] * 8 >= ((int64_t)lay->height * lay->v[c] + lay->max_v - 1) / lay->max_v &&
-                     (reinterpret_cast<uintptr_t>(work + lay->plane_off[c]) & 7) == 0,
+    SP_ARG_CHECK((reinterpret_cast<uintptr_t>(work + lay->plane_off[c]) & 7) == 0,
                  "sp_jpeg_to_rgb: inconsistent layout");
   hipStream_t s = as_stream(stream);
   const int64_t g1 = (lay->total_blocks + 31) / 32;
@@ -245,4 +335,73 @@ extern "C" int sp_jpeg_to_rgb(const int16_t* coefs, const sp_jpeg_layout* lay, u
   hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, s, *lay, work, rgb,
                      rgb_stride);
   return check_launch("sp_jpeg_to_rgb(color)");
+}
+
+extern "C" int sp_jpeg_batch_plan(const sp_jpeg_layout* lays, int n, sp_jpeg_batch_item* items,
+                                  sp_jpeg_batch_totals* totals) {
+  using namespace sp;
+  return batch_plan(lays, n, items, totals);
+}
+
+extern "C" int sp_jpeg_batch_to_rgb(const int16_t* coefs, int64_t coef_elems, const sp_jpeg_batch_item* items_dev,
+                                    const sp_jpeg_batch_item* items_host, int n, const sp_jpeg_batch_totals* totals,
+                                    uint8_t* work, int64_t work_bytes, uint8_t* rgb, int64_t rgb_bytes,
+                                    int32_t* status, void* stream) {
+  using namespace sp;
+  SP_ARG_CHECK(coefs && items_dev && items_host && totals && work && rgb && status,
+               "sp_jpeg_batch_to_rgb: null args");
+  SP_ARG_CHECK(n >= 1 && n <= SP_JPEG_BATCH_MAX, "sp_jpeg_batch_to_rgb: n = %d outside [1, %d]", n,
+               SP_JPEG_BATCH_MAX);
+  SP_ARG_CHECK((reinterpret_cast<uintptr_t>(coefs) & 1) == 0 && (reinterpret_cast<uintptr_t>(items_dev) & 7) == 0 &&
+                   (reinterpret_cast<uintptr_t>(work) & 15) == 0 && (reinterpret_cast<uintptr_t>(rgb) & 3) == 0 &&
+                   (reinterpret_cast<uintptr_t>(status) & 3) == 0,
+               "sp_jpeg_batch_to_rgb: misaligned buffer");
+  int64_t wg_idct = 0, wg_color = 0;
+  for (int i = 0; i < n; ++i) {
+    const sp_jpeg_batch_item& it = items_host[i];
+    const sp_jpeg_layout& L = it.lay;
+    if (int rc = check_batch_layout(&L, i)) return rc;
+    SP_ARG_CHECK(it.coef_off >= 0 && it.coef_off <= coef_elems && L.total_blocks * 64 <= coef_elems - it.coef_off,
+                 "sp_jpeg_batch_to_rgb: image %d: coefficients [%lld, +%lld) outside %lld elements", i,
+                 (long long)it.coef_off, (long long)(L.total_blocks * 64), (long long)coef_elems);
+    SP_ARG_CHECK(it.work_off >= 0 && (it.work_off & 15) == 0 && it.work_off <= work_bytes &&
+                     L.plane_bytes <= work_bytes - it.work_off,
+                 "sp_jpeg_batch_to_rgb: image %d: planes [%lld, +%lld) misaligned or outside work's %lld bytes", i,
+                 (long long)it.work_off, (long long)L.plane_bytes, (long long)work_bytes);
+    SP_ARG_CHECK(it.rgb_stride >= 3LL * L.width && it.rgb_stride <= (1LL << 40),
+                 "sp_jpeg_batch_to_rgb: image %d: rgb_stride %lld outside [%lld, 2^40]", i,
+                 (long long)it.rgb_stride, 3LL * L.width);
+    // the last row ends after its pixels, not after a full stride
+    const int64_t span = it.rgb_stride * (L.height - 1) + 3LL * L.width;
+    SP_ARG_CHECK(it.rgb_off >= 0 && (it.rgb_off & 3) == 0 && it.rgb_off <= rgb_bytes && span <= rgb_bytes - it.rgb_off,
+                 "sp_jpeg_batch_to_rgb: image %d: RGB [%lld, +%lld) misaligned or outside the arena's %lld bytes", i,
+                 (long long)it.rgb_off, (long long)span, (long long)rgb_bytes);
+    SP_ARG_CHECK(it.first_wg_idct == wg_idct && it.first_wg_color == wg_color,
+                 "sp_jpeg_batch_to_rgb: image %d: first workgroups %d / %d, its predecessors give %lld / %lld", i,
+                 it.first_wg_idct, it.first_wg_color, (long long)wg_idct, (long long)wg_color);
+    wg_idct += idct_wgs(L);
+    wg_color += color_wgs(L);
+    SP_ARG_CHECK(wg_idct <= INT32_MAX && wg_color <= INT32_MAX, "sp_jpeg_batch_to_rgb: too many workgroups");
+    for (int k = 0; k < i; ++k) {
+      const sp_jpeg_batch_item& o = items_host[k];
+      const int64_t ospan = o.rgb_stride * (o.lay.height - 1) + 3LL * o.lay.width;
+      SP_ARG_CHECK(it.coef_off + L.total_blocks * 64 <= o.coef_off || o.coef_off + o.lay.total_blocks * 64 <= it.coef_off,
+                   "sp_jpeg_batch_to_rgb: coefficients of images %d and %d overlap", k, i);
+      SP_ARG_CHECK(it.work_off + L.plane_bytes <= o.work_off || o.work_off + o.lay.plane_bytes <= it.work_off,
+                   "sp_jpeg_batch_to_rgb: planes of images %d and %d overlap", k, i);
+      SP_ARG_CHECK(it.rgb_off + span <= o.rgb_off || o.rgb_off + ospan <= it.rgb_off,
+                   "sp_jpeg_batch_to_rgb: RGB ranges of images %d and %d overlap", k, i);
+    }
+  }
+  SP_ARG_CHECK(totals->wg_idct == wg_idct && totals->wg_color == wg_color,
+               "sp_jpeg_batch_to_rgb: totals give %lld / %lld workgroups, the table %lld / %lld",
+               (long long)totals->wg_idct, (long long)totals->wg_color, (long long)wg_idct, (long long)wg_color);
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(jpeg_idct_batch_kernel, dim3((unsigned)wg_idct), dim3(256), 0, s, coefs, coef_elems, items_dev, n,
+                     work, work_bytes, status);
+  int rc = check_launch("sp_jpeg_batch_to_rgb(idct)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(jpeg_color_batch_kernel, dim3((unsigned)wg_color), dim3(256), 0, s, items_dev, n, work, work_bytes,
+                     rgb, rgb_bytes);
+  return check_launch("sp_jpeg_batch_to_rgb(color)");
 }

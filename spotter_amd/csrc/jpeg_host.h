@@ -11,6 +11,7 @@
 
 #include <climits>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 
 #include "../../include/spotter_hip.h"
@@ -987,6 +988,94 @@ inline int enc_finish(const sp_jpeg_enc_layout& L, const uint8_t* bits, int64_t 
   }
   b1(0xFF), b1(0xD9);
   *out_len = o - out;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ batch plan
+// Host half of the batched coefficients → RGB call (sp_jpeg_batch_plan; sp_jpeg_batch_to_rgb's argument checks use
+// the same layout rules). Here, not in jpeg.hip, so tools/sanitize/jpeg_batch_plan.cpp runs it under ASan / UBSan.
+#define SP_JPEG_REQUIRE(cond, ...)   \
+  do {                               \
+    if (!(cond)) {                   \
+      ::sp::set_error(__VA_ARGS__);  \
+      return -1;                     \
+    }                                \
+  } while (0)
+
+// sp_jpeg_to_rgb's layout consistency rule: every component's plane covers its part of the image.
+inline int check_layout(const sp_jpeg_layout* lay, const char* who) {
+  SP_JPEG_REQUIRE(lay->ncomp == 1 || lay->ncomp == 3, "%s: ncomp %d", who, lay->ncomp);
+  for (int c = 0; c < lay->ncomp; ++c)
+    SP_JPEG_REQUIRE(lay->h[c] >= 1 && lay->v[c] >= 1 && lay->max_h >= lay->h[c] && lay->max_v >= lay->v[c] &&
+                        (int64_t)lay->bw[c] * 8 >= ((int64_t)lay->width * lay->h[c] + lay->max_h - 1) / lay->max_h &&
+                        (int64_t)lay->bh[c] * 8 >= ((int64_t)lay->height * lay->v[c] + lay->max_v - 1) / lay->max_v,
+                    "%s: inconsistent layout", who);
+  return 0;
+}
+
+// What the batched kernels also take from the table and the single-image call takes on trust: a frame of at least
+// one pixel, the sampling forms chroma_at implements, and blocks and planes packed in component order inside
+// total_blocks / plane_bytes with 8-byte aligned planes (what the parser writes). The block grid is bounded first
+// (the largest frame at 4x sampling is 8188 blocks across), so the sums below cannot overflow.
+constexpr int kMaxBlocksAcross = 1 << 14;
+inline int check_batch_layout(const sp_jpeg_layout* lay, int i) {
+  char who[48];
+  snprintf(who, sizeof(who), "sp_jpeg_batch: image %d", i);
+  if (int rc = check_layout(lay, who)) return rc;
+  SP_JPEG_REQUIRE(lay->width >= 1 && lay->height >= 1 && lay->width <= SP_JPEG_MAX_DIMENSION &&
+                      lay->height <= SP_JPEG_MAX_DIMENSION,
+                  "%s: %d x %d pixels", who, lay->width, lay->height);
+  SP_JPEG_REQUIRE(lay->h[0] == lay->max_h && lay->v[0] == lay->max_v, "%s: luma below the maximum sampling", who);
+  SP_JPEG_REQUIRE(lay->plane_bytes >= 0 && lay->plane_bytes <= 3LL * 64 * kMaxBlocksAcross * kMaxBlocksAcross,
+                  "%s: plane_bytes %lld", who, (long long)lay->plane_bytes);
+  int64_t blocks = 0, bytes = 0;
+  for (int c = 0; c < lay->ncomp; ++c) {
+    SP_JPEG_REQUIRE(lay->max_h % lay->h[c] == 0 && lay->max_v % lay->v[c] == 0 && lay->max_h / lay->h[c] <= 2 &&
+                        lay->max_v / lay->v[c] <= 2,
+                    "%s: chroma sampling ratio other than 1 or 2", who);
+    SP_JPEG_REQUIRE(lay->bw[c] >= 1 && lay->bh[c] >= 1 && lay->bw[c] <= kMaxBlocksAcross &&
+                        lay->bh[c] <= kMaxBlocksAcross && lay->block_off[c] == blocks && lay->plane_off[c] >= bytes &&
+                        lay->plane_off[c] <= lay->plane_bytes && (lay->plane_off[c] & 7) == 0,
+                    "%s: blocks or planes of component %d not packed in order", who, c);
+    blocks += (int64_t)lay->bw[c] * lay->bh[c];
+    bytes = lay->plane_off[c] + (int64_t)lay->bw[c] * lay->bh[c] * 64;
+  }
+  SP_JPEG_REQUIRE(lay->total_blocks == blocks && lay->plane_bytes >= bytes, "%s: total_blocks / plane_bytes", who);
+  return 0;
+}
+
+inline int64_t idct_wgs(const sp_jpeg_layout& L) {
+  return (L.total_blocks + SP_JPEG_BATCH_IDCT_BLOCKS - 1) / SP_JPEG_BATCH_IDCT_BLOCKS;
+}
+inline int64_t color_wgs(const sp_jpeg_layout& L) {
+  return ((int64_t)L.width * L.height + SP_JPEG_BATCH_COLOR_PX - 1) / SP_JPEG_BATCH_COLOR_PX;
+}
+
+
+inline int batch_plan(const sp_jpeg_layout* lays, int n, sp_jpeg_batch_item* items, sp_jpeg_batch_totals* totals) {
+  SP_JPEG_REQUIRE(lays && items && totals, "sp_jpeg_batch_plan: null args");
+  SP_JPEG_REQUIRE(n >= 1 && n <= SP_JPEG_BATCH_MAX, "sp_jpeg_batch_plan: n = %d outside [1, %d]", n,
+                  SP_JPEG_BATCH_MAX);
+  sp_jpeg_batch_totals t = {0, 0, 0, 0, 0};
+  for (int i = 0; i < n; ++i) {
+    if (int rc = check_batch_layout(&lays[i], i)) return rc;
+    sp_jpeg_batch_item& it = items[i];
+    it.lay = lays[i];
+    it.coef_off = t.coef_elems;
+    it.work_off = t.work_bytes;
+    it.rgb_off = t.rgb_bytes;
+    it.rgb_stride = 3LL * lays[i].width;
+    it.first_wg_idct = (int32_t)t.wg_idct;
+    it.first_wg_color = (int32_t)t.wg_color;
+    t.coef_elems += lays[i].total_blocks * 64;
+    t.work_bytes += (lays[i].plane_bytes + 15) & ~15LL;
+    t.rgb_bytes += (it.rgb_stride * lays[i].height + 255) & ~255LL;
+    t.wg_idct += idct_wgs(lays[i]);
+    t.wg_color += color_wgs(lays[i]);
+    SP_JPEG_REQUIRE(t.wg_idct <= INT32_MAX && t.wg_color <= INT32_MAX,
+                    "sp_jpeg_batch_plan: more than 2^31 - 1 workgroups at image %d", i);
+  }
+  *totals = t;
   return 0;
 }
 

@@ -9,6 +9,9 @@ Pillow's libjpeg-turbo, bit for bit (tests/test_jpeg.py, tests/test_gpu_kernels.
 needs) that also carries its device copy, which SpotterImageProcessor then uses instead of uploading it
 again. JPEG forms the library does not decode (CMYK, 12-bit, arithmetic coding, ...) and other image formats
 keep the reference's host decode: UnsupportedJpeg is raised and open_image falls back to Pillow's Image.open for that image.
+`JpegDecoder.decode_many(datas)` decodes a list of files together (host entropy decode in a thread pool, one upload,
+sp_jpeg_batch_to_rgb's two launches and one status readback per chunk of up to 64 files) with decode()'s outcome per
+file; spotter_amd/bulk.py builds the bulk pipeline on it.
 
 Opt-in (`JpegDecoder(device, entropy="gpu")`, or SPOTTER_JPEG_ENTROPY=gpu for the decoders open_image / image_module
 create): baseline files with one interleaved scan are entropy-decoded on the GPU too (sp_jpeg_entropy_pack on the
@@ -18,14 +21,15 @@ word is non-zero, takes the host entropy decode, so the pixels and the exception
 from __future__ import annotations
 
 import ctypes as C
+import os
 import threading
 import types
 
 import numpy as np
 import torch
 
-from ._lib import (SP_JPEG_NOT_ELIGIBLE, SP_JPEG_PKG_SMALL, SP_JPEG_UNSUPPORTED, SpJpegEncLayout, SpJpegLayout,
-                   SpJpegScan, lib)
+from ._lib import (SP_JPEG_BATCH_MAX, SP_JPEG_NOT_ELIGIBLE, SP_JPEG_PKG_SMALL, SP_JPEG_UNSUPPORTED, SpJpegBatchItem,
+                   SpJpegBatchTotals, SpJpegEncLayout, SpJpegLayout, SpJpegScan, lib)
 from .config import check_jpeg_entropy, jpeg_entropy_from_env
 
 
@@ -52,6 +56,14 @@ def _check_pixels(lay) -> None:
 KEEP_COEFS = 1 << 25  # int16 coefficients (64 MiB pinned + 64 MiB device): a 4K 4:4:4 frame fits
 KEEP_WORK = 1 << 26   # bytes of component planes
 KEEP_PKG = 1 << 26    # bytes of scan package (pinned + device) and of entropy workspace, entropy="gpu"
+KEEP_ARENA = 1 << 27  # bytes of RGB a decode_many chunk may produce (its arena is allocated per chunk, not kept)
+# int16 elements of the kept coefficient buffer a full decode_many table takes (it travels behind the coefficients)
+_TABLE_ELEMS = (SP_JPEG_BATCH_MAX * C.sizeof(SpJpegBatchItem) + 1) // 2 + 8
+
+
+def default_decode_workers() -> int:
+    """decode_many's default entropy-decode pool size: the CPUs this process may run on, 16 at the most."""
+    return max(1, min(16, len(os.sched_getaffinity(0))))
 
 
 def _buf(data):
@@ -160,6 +172,11 @@ class JpegDecoder:
         self._done = None  # event: the last decode's kernels are done with the device buffers
         self._status = torch.zeros(1, dtype=torch.int32, device=self.dev)  # sp_jpeg_to_rgb's envelope flag
         self._status_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+        # decode_many: one status word per image of a chunk, the counters, the entropy-decode pool
+        self._bstatus = torch.zeros(SP_JPEG_BATCH_MAX, dtype=torch.int32, device=self.dev)
+        self._bstatus_host = torch.zeros(SP_JPEG_BATCH_MAX, dtype=torch.int32, pin_memory=True)
+        self.batch_stats = {"calls": 0, "chunks": 0, "images": 0, "h2d_bytes": 0, "refused": 0, "flagged": 0}
+        self._workers = None
 
     def _buffers(self, n_coef, n_work):
         """(pinned host coefficients, device coefficients, device planes, kept?) for one decode."""
@@ -235,6 +252,151 @@ class JpegDecoder:
                 raise UnsupportedJpeg("coefficients outside the IDCT range shared with libjpeg-turbo's SIMD "
                                       "code (corrupt or crafted data): left to Pillow")
             return out
+
+    def decode_many(self, datas, max_workers=None) -> list:
+        """Many JPEGs → one entry per input, in input order: the uint8 [H, W, 3] device tensor decode() returns for
+        that file (a view into one arena tensor per chunk, on torch's current stream), or the UnsupportedJpeg
+        decode() raises for it, returned and not raised, so one bad file does not cost the batch. Any other error
+        is raised as decode() raises it.
+
+        Every file is parsed for its layout; the accepted ones are laid out by sp_jpeg_batch_plan in chunks of at
+        most SP_JPEG_BATCH_MAX files whose totals fit the kept buffers (KEEP_COEFS / KEEP_WORK / KEEP_ARENA; a file
+        larger than those runs as a chunk of its own through buffers of that call). Per chunk: the host entropy
+        decode of its files in a thread pool (max_workers; default min(16, CPUs this process may use)), each into
+        its slice of the pinned staging buffer, one H2D copy of coefficients plus table, one sp_jpeg_batch_to_rgb
+        (two launches), one readback of the status words, one event wait. A decoder created with entropy="gpu"
+        uses the host entropy decode here too: batching the GPU entropy decode across images is not implemented.
+        `batch_stats` counts the calls, chunks (= launch chains), images, h2d_bytes, and the files returned as
+        UnsupportedJpeg by the parser ("refused") and by the IDCT envelope ("flagged"); `stats` is not touched."""
+        L = lib()
+        bufs = [_buf(d) for d in datas]
+        out: list = [None] * len(bufs)
+        lays: list = [None] * len(bufs)
+        for i, (ptr, n, _) in enumerate(bufs):
+            lay = SpJpegLayout()
+            rc = L.sp_jpeg_decode_coefs(ptr, n, C.byref(lay), None, 0)
+            if rc == SP_JPEG_UNSUPPORTED:
+                out[i] = UnsupportedJpeg(L.sp_last_error().decode(errors="replace"))
+                continue
+            if rc:
+                raise RuntimeError(f"sp_jpeg_decode_coefs: {L.sp_last_error().decode(errors='replace')}")
+            try:
+                _check_pixels(lay)
+            except UnsupportedJpeg as e:
+                out[i] = e
+                continue
+            lays[i] = lay
+        # greedy chunks in input order, by count and by the three buffer budgets
+        chunks, cur_chunk, tot = [], [], [0, 0, 0]
+        for i, lay in enumerate(lays):
+            if lay is None:
+                continue
+            need = (lay.total_blocks * 64, (lay.plane_bytes + 15) & ~15, (3 * lay.width * lay.height + 255) & ~255)
+            if cur_chunk and (len(cur_chunk) == SP_JPEG_BATCH_MAX or tot[0] + need[0] + _TABLE_ELEMS > KEEP_COEFS
+                              or tot[1] + need[1] > KEEP_WORK or tot[2] + need[2] > KEEP_ARENA):
+                chunks.append(cur_chunk)
+                cur_chunk, tot = [], [0, 0, 0]
+            cur_chunk.append(i)
+            tot = [a + b for a, b in zip(tot, need)]
+        if cur_chunk:
+            chunks.append(cur_chunk)
+        workers = max_workers if max_workers is not None else default_decode_workers()
+        if workers < 1:
+            raise ValueError("max_workers must be at least 1")
+        st = self.batch_stats
+        refused = sum(o is not None for o in out)
+        with self._lock:
+            st["calls"] += 1
+            st["refused"] += refused
+            for idx in chunks:
+                self._decode_chunk(L, idx, bufs, lays, out, workers)
+        return out
+
+    def _decode_chunk(self, L, idx, bufs, lays, out, workers):
+        """One chunk of decode_many (lock held): out[i] for i in idx."""
+        n = len(idx)
+        arr = (SpJpegLayout * n)(*[lays[i] for i in idx])
+        items = (SpJpegBatchItem * n)()
+        totals = SpJpegBatchTotals()
+        if L.sp_jpeg_batch_plan(arr, n, items, C.byref(totals)):
+            raise RuntimeError(f"sp_jpeg_batch_plan: {L.sp_last_error().decode(errors='replace')}")
+        tab_off = (totals.coef_elems + 7) & ~7  # the table follows the coefficients, 16-byte aligned
+        tab_bytes = C.sizeof(items)
+        nelem = tab_off + (tab_bytes + 1) // 2
+        host, coefs, work, kept = self._buffers(nelem, totals.work_bytes)
+        if kept and self._copied is not None:
+            self._copied.synchronize()  # the pinned buffer is free again
+        hp = host.data_ptr()
+
+        def entropy(k):
+            ptr, nb, _ = bufs[idx[k]]
+            lay = SpJpegLayout()  # sp_jpeg_decode_coefs rewrites the layout: a private copy per thread
+            rc = L.sp_jpeg_decode_coefs(ptr, nb, C.byref(lay), hp + 2 * items[k].coef_off,
+                                        lays[idx[k]].total_blocks * 64)
+            if rc == 0:
+                items[k].lay.quant = lay.quant  # the tables as latched at each component's first scan
+            return rc, L.sp_last_error()
+
+        if workers > 1 and n > 1:
+            rcs = list(self._pool(workers).map(entropy, range(n)))
+        else:
+            rcs = [entropy(k) for k in range(n)]
+        bad = {}
+        for k, (rc, msg) in enumerate(rcs):
+            if rc == SP_JPEG_UNSUPPORTED:
+                # its slice holds whatever the decoder wrote before it stopped: the kernels run over it (any int16
+                # is a valid input) and the result is dropped
+                bad[k] = UnsupportedJpeg(msg.decode(errors="replace"))
+            elif rc:
+                raise RuntimeError(f"sp_jpeg_decode_coefs: {msg.decode(errors='replace')}")
+        C.memmove(hp + 2 * tab_off, items, tab_bytes)
+        cur = torch.cuda.current_stream(self.dev)
+        if kept and self._done is not None:
+            cur.wait_event(self._done)  # another stream's previous decode may still read the buffers
+        coefs[:nelem].copy_(host[:nelem], non_blocking=True)
+        copied = torch.cuda.Event()
+        copied.record()
+        arena = torch.empty(totals.rgb_bytes, dtype=torch.uint8, device=self.dev)
+        status = self._bstatus[:n]
+        status.zero_()
+        rc = L.sp_jpeg_batch_to_rgb(coefs.data_ptr(), totals.coef_elems, coefs.data_ptr() + 2 * tab_off, items, n,
+                                    C.byref(totals), work.data_ptr(), work.numel(), arena.data_ptr(), arena.numel(),
+                                    status.data_ptr(), cur.cuda_stream)
+        if rc:
+            raise RuntimeError(f"sp_jpeg_batch_to_rgb: {L.sp_last_error().decode(errors='replace')}")
+        self._bstatus_host[:n].copy_(status, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(cur)
+        done.synchronize()
+        if kept:
+            self._copied, self._done = copied, done
+        flags = self._bstatus_host[:n].tolist()
+        st = self.batch_stats
+        st["chunks"] += 1
+        st["images"] += n
+        st["h2d_bytes"] += 2 * nelem
+        for k, i in enumerate(idx):
+            if k in bad:
+                st["refused"] += 1
+                out[i] = bad[k]
+            elif flags[k]:
+                st["flagged"] += 1
+                out[i] = UnsupportedJpeg("coefficients outside the IDCT range shared with libjpeg-turbo's SIMD "
+                                         "code (corrupt or crafted data): left to Pillow")
+            else:
+                it = items[k]
+                H, W = it.lay.height, it.lay.width
+                out[i] = arena[it.rgb_off:it.rgb_off + H * W * 3].view(H, W, 3)
+
+    def _pool(self, workers):
+        """The decoder's entropy-decode thread pool (created on first use, replaced when the size changes)."""
+        import concurrent.futures as cf
+
+        if self._workers is None or self._workers[0] != workers:
+            if self._workers is not None:
+                self._workers[1].shutdown(wait=True)
+            self._workers = (workers, cf.ThreadPoolExecutor(max_workers=workers, thread_name_prefix="spotter-jpeg"))
+        return self._workers[1]
 
     def _decode_gpu_entropy(self, L, ptr, n, out):
         """entropy="gpu": pack on the host into the reused pinned buffer, copy the package asynchronously, run the

@@ -573,6 +573,65 @@ int sp_jpeg_entropy_emulate(const uint8_t* pkg, const sp_jpeg_scan* scan, const 
                             int64_t coef_elems, int32_t* status, int32_t* rounds);
 
 /*
+ * The same decode over up to SP_JPEG_BATCH_MAX images in one launch chain (added under ABI v20): eight kernel
+ * launches whatever n is, after one memset per contiguous run of coefficient ranges (one for a table as
+ * sp_jpeg_batch_plan packs it). The images' packages share one buffer, their entropy workspaces another, their
+ * coefficients the buffer sp_jpeg_batch_to_rgb reads; one table row per image says where its parts lie and which
+ * workgroups of the two launch shapes are its own (a workgroup never spans two images and finds its row by the
+ * uniform binary search sp_jpeg_batch_to_rgb uses).
+ */
+typedef struct {
+  sp_jpeg_scan scan;       /* as sp_jpeg_entropy_pack filled it; tab_off / seg_off / stream_off relative to pkg_off */
+  int32_t h[3], v[3];      /* the layout fields the block geometry needs (sp_jpeg_layout h, v, bw, bh) */
+  int32_t bw[3], bh[3];
+  int64_t block_off[3];    /* sp_jpeg_layout block_off */
+  int64_t total_blocks;    /* the image's coefficient range is total_blocks * 64 int16 from coef_off */
+  int64_t geom[28];        /* the kernels' geometry record (csrc/jpeg_entropy_core.h Geom) derived from the fields
+                              above by the plan; the check recomputes it and refuses a row where it differs */
+  int64_t pkg_off;        /* byte offset of its package in the shared package buffer, a multiple of 16 */
+  int64_t work_off;        /* byte offset of its entropy workspace in the shared one, a multiple of 16 */
+  int64_t coef_off;        /* first int16 element of its coefficients (sp_jpeg_batch_item coef_off) */
+  int64_t dc_nchunk;       /* chunks of its DC pass (one thread each) */
+  int32_t first_wg_sub;    /* its first workgroup in the per-subsequence launches: prefix sum of ceil(nsub / 256) */
+  int32_t first_wg_dc;     /* the same for the DC launches: prefix sum of ceil(dc_nchunk / 256) */
+} sp_jpeg_entropy_item;
+typedef struct {
+  int64_t pkg_bytes;       /* bytes of the shared package buffer */
+  int64_t work_bytes;      /* bytes of the shared entropy workspace */
+  int64_t wg_sub;          /* workgroups of a per-subsequence launch */
+  int64_t wg_dc;           /* workgroups of a DC launch */
+} sp_jpeg_entropy_totals;
+/* Host: lay out n images for sp_jpeg_entropy_batch_decode. scans[i] / lays[i] as sp_jpeg_entropy_pack filled them,
+ * batch_items[i].coef_off from sp_jpeg_batch_plan. Refused with -1 and a message: a NULL pointer, n outside
+ * [1, SP_JPEG_BATCH_MAX], a scan sp_jpeg_entropy_decode would refuse, a coefficient range (up to the next image's, or
+ * as sp_jpeg_batch_plan packs them) that does not hold total_blocks * 64, more than 2^31 - 1 workgroups. No device
+ * call. */
+int sp_jpeg_entropy_batch_plan(const sp_jpeg_scan* scans, const sp_jpeg_layout* lays,
+                               const sp_jpeg_batch_item* batch_items, int n, sp_jpeg_entropy_item* ent_items,
+                               sp_jpeg_entropy_totals* ent_totals);
+/* Host: the check sp_jpeg_entropy_batch_decode runs on the host copy of the table before it launches anything: every
+ * row's scan as sp_jpeg_entropy_decode checks it, the row's geometry fields consistent with the scan, every package /
+ * workspace / coefficient range aligned and inside its buffer, the ranges of one buffer pairwise disjoint, both prefix
+ * columns and *totals what the rows give. 0, or -1 and a message. No device call. */
+int sp_jpeg_entropy_batch_check(const sp_jpeg_entropy_item* items, int n, const sp_jpeg_entropy_totals* totals,
+                                int64_t pkg_bytes, int64_t work_bytes, int64_t coef_elems);
+/* Device: the launch chain for the whole chunk. pkgs_dev: the packages at their pkg_off (16-byte aligned), items_dev
+ * the device copy of the table (8-byte aligned; it may travel behind the packages in the same upload), items_host
+ * the same bytes on the host, read only by sp_jpeg_entropy_batch_check. work 16-byte aligned. status: device int32
+ * [n], zeroed by the caller: status[i] gets image i's reason bits (as sp_jpeg_entropy_decode's) and nobody else's;
+ * it is the array sp_jpeg_batch_to_rgb ORs its envelope flag into afterwards. Asynchronous on `stream`; allocates
+ * nothing, copies nothing. */
+int sp_jpeg_entropy_batch_decode(const uint8_t* pkgs_dev, int64_t pkg_bytes, const sp_jpeg_entropy_item* items_dev,
+                                 const sp_jpeg_entropy_item* items_host, int n, const sp_jpeg_entropy_totals* totals,
+                                 uint8_t* work, int64_t work_bytes, int16_t* coefs, int64_t coef_elems,
+                                 int32_t* status, void* stream);
+/* Host: sp_jpeg_entropy_batch_decode's passes on the CPU, walking the table workgroup by workgroup as the kernels do
+ * (the binary search included), over the same per-subsequence code. pkgs, work, coefs, status are host memory. */
+int sp_jpeg_entropy_batch_emulate(const uint8_t* pkgs, int64_t pkg_bytes, const sp_jpeg_entropy_item* items, int n,
+                                  const sp_jpeg_entropy_totals* totals, uint8_t* work, int64_t work_bytes,
+                                  int16_t* coefs, int64_t coef_elems, int32_t* status);
+
+/*
  * JPEG encode (ABI v12): serve.py:139-142 `image.save(buffer, format="JPEG")`, which Pillow runs through
  * libjpeg-turbo with quality 75 (or the caller's), 4:2:0 (or the caller's subsampling), the ISLOW forward DCT,
  * the Annex K Huffman tables and a JFIF header. Split as the hardware wants it: colour conversion,

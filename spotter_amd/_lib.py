@@ -105,6 +105,16 @@ class SpJpegScan(C.Structure):
     ]
 
 
+class SpJpegEntropyItem(C.Structure):
+    _fields_ = [("scan", SpJpegScan), ("h", i32 * 3), ("v", i32 * 3), ("bw", i32 * 3), ("bh", i32 * 3),
+                ("block_off", i64 * 3), ("total_blocks", i64), ("geom", i64 * 28), ("pkg_off", i64), ("work_off", i64),
+                ("coef_off", i64), ("dc_nchunk", i64), ("first_wg_sub", i32), ("first_wg_dc", i32)]
+
+
+class SpJpegEntropyTotals(C.Structure):
+    _fields_ = [("pkg_bytes", i64), ("work_bytes", i64), ("wg_sub", i64), ("wg_dc", i64)]
+
+
 class SpJpegEncLayout(C.Structure):
     _fields_ = [
         ("width", i32), ("height", i32), ("quality", i32), ("h0", i32), ("v0", i32),
@@ -212,6 +222,14 @@ _SIGS = {
     "sp_jpeg_entropy_pack": (i32, [vp, i64, C.POINTER(SpJpegLayout), C.POINTER(SpJpegScan), vp, i64]),
     "sp_jpeg_entropy_decode": (i32, [vp, C.POINTER(SpJpegScan), C.POINTER(SpJpegLayout), vp, i64, vp, i64, vp, vp]),
     "sp_jpeg_entropy_emulate": (i32, [vp, C.POINTER(SpJpegScan), C.POINTER(SpJpegLayout), vp, i64, vp, vp]),
+    "sp_jpeg_entropy_batch_plan": (i32, [C.POINTER(SpJpegScan), C.POINTER(SpJpegLayout), C.POINTER(SpJpegBatchItem), i32,
+                                         C.POINTER(SpJpegEntropyItem), C.POINTER(SpJpegEntropyTotals)]),
+    "sp_jpeg_entropy_batch_check": (i32, [C.POINTER(SpJpegEntropyItem), i32, C.POINTER(SpJpegEntropyTotals), i64, i64,
+                                          i64]),
+    "sp_jpeg_entropy_batch_decode": (i32, [vp, i64, vp, C.POINTER(SpJpegEntropyItem), i32,
+                                           C.POINTER(SpJpegEntropyTotals), vp, i64, vp, i64, vp, vp]),
+    "sp_jpeg_entropy_batch_emulate": (i32, [vp, i64, C.POINTER(SpJpegEntropyItem), i32,
+                                            C.POINTER(SpJpegEntropyTotals), vp, i64, vp, i64, vp]),
     "sp_jpeg_enc_plan": (i32, [i32, i32, i32, i32, C.POINTER(SpJpegEncLayout)]),
     "sp_jpeg_enc_rgb": (i32, [vp, i64, i32, C.POINTER(SpJpegEncLayout), vp, i64, vp, i64, vp, vp]),
     "sp_jpeg_enc_max_bytes": (i64, [C.POINTER(SpJpegEncLayout), i64, i64]),

@@ -5,7 +5,8 @@ overlapped with the forward of the current one.
     for res in det.detect(paths_or_bytes):
         ...  # {"size": (w, h), "scores", "labels", "boxes"} or {"error": str}, in input order
 
-    python -m spotter_amd.bulk --model NAME [--precision P] [--batch 32] [--threshold 0.5] --out results.jsonl PATH...
+    python -m spotter_amd.bulk --model NAME [--precision P] [--batch 32] [--threshold 0.5]
+                               [--jpeg-entropy {host,gpu,auto}] --out results.jsonl PATH...
 
 Per chunk of `batch` files, stage A (one host thread with a stream of its own) reads the files and decodes them with
 JpegDecoder.decode_many: one H2D copy, two launches and one status readback for the chunk. What decode_many returns
@@ -46,12 +47,18 @@ def _pillow_rgb(data: bytes):
 class BulkDetector:
     """model / processor: a SpotterForObjectDetection (any precision, batch_invariant or not) and a
     SpotterImageProcessor, or anything with their call surface. decoder: the JpegDecoder to use (default: the
-    device's shared host-entropy decoder); decode_workers: decode_many's max_workers. `stage_seconds` keeps the busy
-    time of stage A and stage B of every chunk of the last detect() ("a" / "b", seconds)."""
+    device's shared decoder of entropy mode jpeg_entropy: "host", the default, or "gpu" / "auto", which decode the
+    baseline files of a chunk in one GPU launch chain); decode_workers: decode_many's max_workers.
+    `stage_seconds` keeps the busy time of stage A and stage B of every chunk of the last detect() ("a" / "b",
+    seconds)."""
 
-    def __init__(self, model, processor, batch=32, threshold=0.5, decode_workers=None, decoder=None, device=None):
+    def __init__(self, model, processor, batch=32, threshold=0.5, decode_workers=None, decoder=None, device=None,
+                 jpeg_entropy="host"):
+        from .config import check_jpeg_entropy
+
         if int(batch) < 1:
             raise ValueError("batch must be at least 1")
+        self.jpeg_entropy = check_jpeg_entropy(jpeg_entropy)
         self.model, self.processor = model, processor
         self.batch, self.threshold, self.decode_workers = int(batch), float(threshold), decode_workers
         self._decoder, self._device = decoder, device
@@ -66,7 +73,7 @@ class BulkDetector:
         if self._decoder is None:
             from .jpeg import decoder
 
-            self._decoder = decoder(self._device)
+            self._decoder = decoder(self._device, self.jpeg_entropy)
         dev = getattr(self._decoder, "dev", None)
         if dev is None or torch.device(dev).type != "cuda":
             return None
@@ -181,16 +188,21 @@ def _detector(args):
 
     model = SpotterForObjectDetection.from_pretrained(args.model, precision=args.precision)
     proc = SpotterImageProcessor.from_pretrained(args.model)
-    return BulkDetector(model, proc, batch=args.batch, threshold=args.threshold), model.config.id2label
+    return BulkDetector(model, proc, batch=args.batch, threshold=args.threshold,
+                        jpeg_entropy=args.jpeg_entropy), model.config.id2label
 
 
 def main(argv=None, make_detector=_detector) -> int:
     """make_detector(args) → (BulkDetector, id2label): the tests put a host stand-in here."""
+    from .config import JPEG_ENTROPY_MODES, jpeg_entropy_from_env
+
     ap = argparse.ArgumentParser(prog="python -m spotter_amd.bulk", description=__doc__.split("\n\n")[0])
     ap.add_argument("--model", required=True, help="as from_pretrained: a directory, a cached hub id, synthetic:<preset>")
     ap.add_argument("--precision", default="fp32")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--threshold", type=float, default=0.5)
+    ap.add_argument("--jpeg-entropy", choices=JPEG_ENTROPY_MODES, default=jpeg_entropy_from_env(),
+                    help="where baseline JPEGs are Huffman-decoded (default: SPOTTER_JPEG_ENTROPY, i.e. host)")
     ap.add_argument("--out", required=True, help="JSON lines, one per file")
     ap.add_argument("paths", nargs="+", metavar="PATH", help="files, or directories walked in sorted order")
     args = ap.parse_args(argv)

@@ -11,7 +11,8 @@ again. JPEG forms the library does not decode (CMYK, 12-bit, arithmetic coding, 
 keep the reference's host decode: UnsupportedJpeg is raised and open_image falls back to Pillow's Image.open for that image.
 `JpegDecoder.decode_many(datas)` decodes a list of files together (host entropy decode in a thread pool, one upload,
 sp_jpeg_batch_to_rgb's two launches and one status readback per chunk of up to 64 files) with decode()'s outcome per
-file; spotter_amd/bulk.py builds the bulk pipeline on it.
+file; spotter_amd/bulk.py builds the bulk pipeline on it. On an entropy="gpu" decoder the eligible
+files of a chunk are entropy-decoded on the device in one launch chain (sp_jpeg_entropy_batch_decode).
 
 Opt-in (`JpegDecoder(device, entropy="gpu")`, or SPOTTER_JPEG_ENTROPY=gpu for the decoders open_image / image_module
 create): baseline files with one interleaved scan are entropy-decoded on the GPU too (sp_jpeg_entropy_pack on the
@@ -29,7 +30,8 @@ import numpy as np
 import torch
 
 from ._lib import (SP_JPEG_BATCH_MAX, SP_JPEG_NOT_ELIGIBLE, SP_JPEG_PKG_SMALL, SP_JPEG_UNSUPPORTED, SpJpegBatchItem,
-                   SpJpegBatchTotals, SpJpegEncLayout, SpJpegLayout, SpJpegScan, lib)
+                   SpJpegBatchTotals, SpJpegEncLayout, SpJpegEntropyItem, SpJpegEntropyTotals, SpJpegLayout, SpJpegScan,
+                   lib)
 from .config import check_jpeg_entropy, jpeg_entropy_from_env
 
 
@@ -59,6 +61,27 @@ KEEP_PKG = 1 << 26    # bytes of scan package (pinned + device) and of entropy w
 KEEP_ARENA = 1 << 27  # bytes of RGB a decode_many chunk may produce (its arena is allocated per chunk, not kept)
 # int16 elements of the kept coefficient buffer a full decode_many table takes (it travels behind the coefficients)
 _TABLE_ELEMS = (SP_JPEG_BATCH_MAX * C.sizeof(SpJpegBatchItem) + 1) // 2 + 8
+# bytes both tables of a full GPU-entropy chunk take behind its packages in the package buffer
+_ENT_TABLE_BYTES = SP_JPEG_BATCH_MAX * (C.sizeof(SpJpegEntropyItem) + C.sizeof(SpJpegBatchItem)) + 32
+# A scan package without its segment table and stream: six Huffman tables (csrc/jpeg_entropy_core.h DevHuff, 4496
+# bytes: sp_jpeg_scan.seg_off is 6 of them) and the padding; a segment entry (SegEnt) is 16 bytes. Only the size of the
+# buffer the packer is first offered: a wrong guess costs a second pass (SP_JPEG_PKG_SMALL), never a wrong result.
+# tests/test_jpeg_entropy_batch_host.py pins both to the packer's own offsets.
+_PKG_FIXED = 6 * 4496 + 64
+_SEG_BYTES = 16
+# File bytes of a decode_many call from which the scans are packed in the thread pool. Packing runs at about 4 GB/s
+# on one thread (32 files of 50-120 KB: 0.4 ms), so below this the pool's hand-offs cost more than they spread:
+# measured on 32 such files, decode_many ran 1.6-1.75x faster packing on the calling thread.
+PACK_POOL_BYTES = 1 << 24
+
+
+def _new_batch_stats() -> dict:
+    return {"calls": 0, "chunks": 0, "images": 0, "h2d_bytes": 0, "refused": 0, "flagged": 0, "gpu": 0, "host": 0,
+            "fallback": {}}
+
+
+def _a16(v: int) -> int:
+    return (v + 15) & ~15
 
 
 def default_decode_workers() -> int:
@@ -175,7 +198,7 @@ class JpegDecoder:
         # decode_many: one status word per image of a chunk, the counters, the entropy-decode pool
         self._bstatus = torch.zeros(SP_JPEG_BATCH_MAX, dtype=torch.int32, device=self.dev)
         self._bstatus_host = torch.zeros(SP_JPEG_BATCH_MAX, dtype=torch.int32, pin_memory=True)
-        self.batch_stats = {"calls": 0, "chunks": 0, "images": 0, "h2d_bytes": 0, "refused": 0, "flagged": 0}
+        self.batch_stats = _new_batch_stats()
         self._workers = None
 
     def _buffers(self, n_coef, n_work):
@@ -264,10 +287,22 @@ class JpegDecoder:
         larger than those runs as a chunk of its own through buffers of that call). Per chunk: the host entropy
         decode of its files in a thread pool (max_workers; default min(16, CPUs this process may use)), each into
         its slice of the pinned staging buffer, one H2D copy of coefficients plus table, one sp_jpeg_batch_to_rgb
-        (two launches), one readback of the status words, one event wait. A decoder created with entropy="gpu"
-        uses the host entropy decode here too: batching the GPU entropy decode across images is not implemented.
-        `batch_stats` counts the calls, chunks (= launch chains), images, h2d_bytes, and the files returned as
-        UnsupportedJpeg by the parser ("refused") and by the IDCT envelope ("flagged"); `stats` is not touched."""
+        (two launches), one readback of the status words, one event wait.
+
+        A decoder created with entropy="gpu" / "auto" first packs the accepted files' scans, SP_JPEG_BATCH_MAX files at
+        a time (sp_jpeg_entropy_pack: no Huffman decode on the host; in the pool from PACK_POOL_BYTES of input on),
+        and runs the eligible ones in GPU-entropy chunks as they fill (greedy, in input order, at most SP_JPEG_BATCH_MAX files within KEEP_PKG for the packages and for the entropy
+        workspace, KEEP_COEFS, KEEP_WORK, KEEP_ARENA; a file beyond them alone): packages and both tables in one
+        H2D copy, sp_jpeg_entropy_batch_decode (one memset, eight launches), sp_jpeg_batch_to_rgb on the same device
+        coefficients, one status readback, one event wait. Files that are not eligible and files whose status word
+        comes back non-zero (any bit, the envelope's included: decode()'s rule) then go through the host chunks
+        above, so every file gives the host path's pixels or its UnsupportedJpeg.
+        `batch_stats` counts the calls, chunks (= launch chains), images, h2d_bytes (what was uploaded), the files
+        returned as UnsupportedJpeg by the parser ("refused") and by the IDCT envelope ("flagged"), and on a
+        GPU-entropy decoder the files decoded by the GPU chain ("gpu"), the ones the packer found not eligible ("host";
+        a file the packer refuses outright is not counted here: the host chunk counts it as "refused") and
+        the ones re-routed to the host by their status word ("fallback": {status word: count}); `stats` is not
+        touched."""
         L = lib()
         bufs = [_buf(d) for d in datas]
         out: list = [None] * len(bufs)
@@ -286,6 +321,13 @@ class JpegDecoder:
                 out[i] = e
                 continue
             lays[i] = lay
+        workers = max_workers if max_workers is not None else default_decode_workers()
+        if workers < 1:
+            raise ValueError("max_workers must be at least 1")
+        refused = sum(o is not None for o in out)
+        if self.entropy != "host":
+            # the GPU-entropy chunks first; what they decoded leaves `lays`, the rest takes the host chunks below
+            self._decode_many_gpu_entropy(L, bufs, lays, out, workers)
         # greedy chunks in input order, by count and by the three buffer budgets
         chunks, cur_chunk, tot = [], [], [0, 0, 0]
         for i, lay in enumerate(lays):
@@ -300,11 +342,7 @@ class JpegDecoder:
             tot = [a + b for a, b in zip(tot, need)]
         if cur_chunk:
             chunks.append(cur_chunk)
-        workers = max_workers if max_workers is not None else default_decode_workers()
-        if workers < 1:
-            raise ValueError("max_workers must be at least 1")
         st = self.batch_stats
-        refused = sum(o is not None for o in out)
         with self._lock:
             st["calls"] += 1
             st["refused"] += refused
@@ -387,6 +425,147 @@ class JpegDecoder:
                 it = items[k]
                 H, W = it.lay.height, it.lay.width
                 out[i] = arena[it.rgb_off:it.rgb_off + H * W * 3].view(H, W, 3)
+
+    def _decode_many_gpu_entropy(self, L, bufs, lays, out, workers):
+        """decode_many on an entropy="gpu" decoder: pack the accepted files, a window of SP_JPEG_BATCH_MAX at a time,
+        and run the eligible ones in GPU-entropy chunks as the windows fill them, so at most two windows' packages are
+        alive at once. out[i] is set and lays[i] cleared for every file the GPU chain decoded with status 0. The lock
+        is held throughout: the pool and the counters are the decoder's."""
+        live = [i for i, lay in enumerate(lays) if lay is not None]
+
+        def pack(i):
+            ptr, nb, _ = bufs[i]
+            lay, scan = SpJpegLayout(), SpJpegScan()
+            lay0 = lays[i]
+            nmcu = (lay0.bw[0] // max(1, lay0.h[0])) * (lay0.bh[0] // max(1, lay0.v[0]))
+            # no package of this file is larger (_PKG_FIXED): one pass; were it, the packer says so and gets its size
+            pkg = np.empty(_PKG_FIXED + _SEG_BYTES * (nmcu + 2) + nb, dtype=np.uint8)
+            rc = L.sp_jpeg_entropy_pack(ptr, nb, C.byref(lay), C.byref(scan), pkg.ctypes.data, pkg.size)
+            if rc == SP_JPEG_PKG_SMALL:
+                pkg = np.empty(scan.pkg_bytes, dtype=np.uint8)
+                rc = L.sp_jpeg_entropy_pack(ptr, nb, C.byref(lay), C.byref(scan), pkg.ctypes.data, pkg.size)
+            return rc, L.sp_last_error(), lay, scan, pkg
+
+        def need(lay, scan):
+            return (_a16(scan.pkg_bytes), _a16(scan.work_bytes), lay.total_blocks * 64, _a16(lay.plane_bytes),
+                    (3 * lay.width * lay.height + 255) & ~255)
+
+        st = self.batch_stats
+        with self._lock:
+            pending, pos = [], 0  # (index, layout, scan, package) of eligible files not yet run, in input order
+            while pos < len(live) or pending:
+                if pos < len(live):
+                    window = live[pos:pos + SP_JPEG_BATCH_MAX]
+                    pos += len(window)
+                    if workers > 1 and len(window) > 1 and sum(bufs[i][1] for i in window) >= PACK_POOL_BYTES:
+                        results = list(self._pool(workers).map(pack, window))
+                    else:
+                        results = [pack(i) for i in window]
+                    for i, (rc, msg, lay, scan, pkg) in zip(window, results):
+                        if rc == 0:
+                            pending.append((i, lay, scan, pkg))
+                        elif rc == SP_JPEG_NOT_ELIGIBLE:
+                            st["host"] += 1  # the host chunk decodes it
+                        elif rc != SP_JPEG_UNSUPPORTED:  # (the host chunk refuses that one by the host rules)
+                            raise RuntimeError(f"sp_jpeg_entropy_pack: {msg.decode(errors='replace')}")
+                # the greedy chunk at the head of `pending`, by count and by the five buffer budgets
+                n, tot = 0, [0] * 5
+                for _, lay, scan, _ in pending:
+                    nd = need(lay, scan)
+                    if n and (n == SP_JPEG_BATCH_MAX or tot[0] + nd[0] + _ENT_TABLE_BYTES > KEEP_PKG
+                              or tot[1] + nd[1] > KEEP_PKG or tot[2] + nd[2] > KEEP_COEFS
+                              or tot[3] + nd[3] > KEEP_WORK or tot[4] + nd[4] > KEEP_ARENA):
+                        break
+                    n += 1
+                    tot = [a + b for a, b in zip(tot, nd)]
+                if n == 0 or (n == len(pending) and n < SP_JPEG_BATCH_MAX and pos < len(live)):
+                    continue  # the chunk is still open and there are files left to pack
+                chunk, pending = pending[:n], pending[n:]
+                self._gpu_entropy_chunk(L, chunk, lays, out)
+
+    def _gpu_entropy_chunk(self, L, chunk, lays, out):
+        """One GPU-entropy chunk (lock held): plan both tables, run the device half, route the results."""
+        n = len(chunk)
+        st = self.batch_stats
+        larr = (SpJpegLayout * n)(*[c[1] for c in chunk])
+        items, totals = (SpJpegBatchItem * n)(), SpJpegBatchTotals()
+        if L.sp_jpeg_batch_plan(larr, n, items, C.byref(totals)):
+            raise RuntimeError(f"sp_jpeg_batch_plan: {L.sp_last_error().decode(errors='replace')}")
+        ent, etot = (SpJpegEntropyItem * n)(), SpJpegEntropyTotals()
+        if L.sp_jpeg_entropy_batch_plan((SpJpegScan * n)(*[c[2] for c in chunk]), larr, items, n, ent, C.byref(etot)):
+            raise RuntimeError(f"sp_jpeg_entropy_batch_plan: {L.sp_last_error().decode(errors='replace')}")
+        arena, flags, h2d = self._run_gpu_entropy_chunk(L, [c[3] for c in chunk], ent, etot, items, totals)
+        st["chunks"] += 1
+        st["h2d_bytes"] += h2d
+        for k, (i, _, _, _) in enumerate(chunk):
+            if flags[k]:  # the GPU result is discarded: the host chunk accepts the file or refuses it
+                st["fallback"][flags[k]] = st["fallback"].get(flags[k], 0) + 1
+                continue
+            it = items[k]
+            H, W = it.lay.height, it.lay.width
+            out[i] = arena[it.rgb_off:it.rgb_off + H * W * 3].view(H, W, 3)
+            lays[i] = None
+            st["gpu"] += 1
+            st["images"] += 1
+
+    def _run_gpu_entropy_chunk(self, L, pkgs, ent, etot, items, totals):
+        """The device half of one GPU-entropy chunk (lock held): (RGB arena, status word per image, bytes uploaded).
+        Packages and both tables go into the pinned package buffer and up in one copy; decode()'s event discipline."""
+        n = len(pkgs)
+        ent_off = _a16(etot.pkg_bytes)
+        tab_off = _a16(ent_off + C.sizeof(ent))
+        nbytes = tab_off + C.sizeof(items)
+        need = {"pkg": (nbytes, KEEP_PKG, torch.uint8), "ent": (etot.work_bytes, KEEP_PKG, torch.uint8),
+                "coefs": (totals.coef_elems, KEEP_COEFS, torch.int16),
+                "work": (totals.work_bytes, KEEP_WORK, torch.uint8)}
+        kept = all(sz <= cap for sz, cap, _ in need.values())
+        g = self._g
+        if kept:
+            if self._copied is not None:
+                self._copied.synchronize()  # the pinned package buffer is free again
+            grow = any(g.get(k) is None or g[k].numel() < sz for k, (sz, _, _) in need.items())
+            grow = grow or g.get("pkg_host") is None or g["pkg_host"].numel() < nbytes
+            if grow and self._done is not None:
+                self._done.synchronize()  # the old buffers may still be read by the previous decode on another stream
+            _grow_kept(g, "pkg_host", nbytes, KEEP_PKG, dtype=torch.uint8, pin_memory=True)
+            for k, (sz, cap, dt) in need.items():
+                _grow_kept(g, k, sz, cap, dtype=dt, device=self.dev)
+            host, dev = g["pkg_host"], {k: g[k] for k in need}
+        else:
+            host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+            dev = {k: torch.empty(max(sz, 16), dtype=dt, device=self.dev) for k, (sz, _, dt) in need.items()}
+        hp = host.data_ptr()
+        for k, pkg in enumerate(pkgs):
+            C.memmove(hp + ent[k].pkg_off, pkg.ctypes.data, ent[k].scan.pkg_bytes)
+        C.memmove(hp + ent_off, ent, C.sizeof(ent))
+        C.memmove(hp + tab_off, items, C.sizeof(items))
+        cur = torch.cuda.current_stream(self.dev)
+        if kept and self._done is not None:
+            cur.wait_event(self._done)  # another stream's previous decode may still read the buffers
+        dev["pkg"][:nbytes].copy_(host[:nbytes], non_blocking=True)
+        copied = torch.cuda.Event()
+        copied.record()
+        arena = torch.empty(totals.rgb_bytes, dtype=torch.uint8, device=self.dev)
+        status = self._bstatus[:n]
+        status.zero_()
+        pp = dev["pkg"].data_ptr()
+        rc = L.sp_jpeg_entropy_batch_decode(pp, etot.pkg_bytes, pp + ent_off, ent, n, C.byref(etot),
+                                            dev["ent"].data_ptr(), dev["ent"].numel(), dev["coefs"].data_ptr(),
+                                            totals.coef_elems, status.data_ptr(), cur.cuda_stream)
+        if rc:
+            raise RuntimeError(f"sp_jpeg_entropy_batch_decode: {L.sp_last_error().decode(errors='replace')}")
+        rc = L.sp_jpeg_batch_to_rgb(dev["coefs"].data_ptr(), totals.coef_elems, pp + tab_off, items, n, C.byref(totals),
+                                    dev["work"].data_ptr(), dev["work"].numel(), arena.data_ptr(), arena.numel(),
+                                    status.data_ptr(), cur.cuda_stream)
+        if rc:
+            raise RuntimeError(f"sp_jpeg_batch_to_rgb: {L.sp_last_error().decode(errors='replace')}")
+        self._bstatus_host[:n].copy_(status, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(cur)
+        done.synchronize()
+        if kept:
+            self._copied, self._done = copied, done
+        return arena, self._bstatus_host[:n].tolist(), nbytes
 
     def _pool(self, workers):
         """The decoder's entropy-decode thread pool (created on first use, replaced when the size changes)."""

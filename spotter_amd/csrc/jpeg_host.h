@@ -541,6 +541,10 @@ struct Decoder {
       if (c < 0) return bad("SOS names an unknown component");
       for (int k = 0; k < i; ++k)
         if (ci[k] == c) return bad("SOS names a component twice");
+      // jdmarker.c get_sos takes the scan's i-th component only from the frame components whose cur_comp_info
+      // slot is still empty, and the slots 0 .. i-1 are filled by then: JERR_BAD_COMPONENT_ID for frame position
+      // c < i, so 2,0,1 or 0,2,1 or a two-component 1,0 are refused while 2,1 and 1,2 are taken
+      if (c < i) return bad("SOS names the frame's components out of order");
       ci[i] = c;
       td[i] = q[2 + 2 * i] >> 4;
       ta[i] = q[2 + 2 * i] & 15;
@@ -550,6 +554,11 @@ struct Decoder {
         memcpy(lay->quant[c], qt[comp[c].tq], sizeof(lay->quant[c]));
         comp[c].latched = true;
       }
+    }
+    if (ns > 1) {  // jdinput.c per_scan_setup: JERR_BAD_MCU_SIZE above D_MAX_BLOCKS_IN_MCU in an interleaved scan
+      int bpm = 0;
+      for (int i = 0; i < ns; ++i) bpm += comp[ci[i]].h * comp[ci[i]].v;
+      if (bpm > jpeg_entropy::kMaxSlots) return bad("more than 10 blocks in an MCU");
     }
     const int Ss = q[1 + 2 * ns], Se = q[2 + 2 * ns], Ah = q[3 + 2 * ns] >> 4, Al = q[3 + 2 * ns] & 15;
     const bool prog = lay->progressive != 0;

@@ -5,7 +5,8 @@ many offsets, byte flips in the headers and in the entropy-coded data, and the s
 or broken encoder produces — huge / zero frame sizes, bad quantisation and Huffman table definitions (DC
 symbols above 15, 16-bit precision codes above 1, counts past the segment), bad scan headers, renumbered or
 displaced restart markers, bogus progressive successive-approximation sequences, stray and reserved markers,
-junk between markers. Used by tests/test_jpeg_corpus.py (ASan/UBSan harness + the Pillow equivalence rule).
+junk between markers. The last entries are not mutations: the files of tests/jpeg_stream_writer.py refused_cases(),
+well-formed streams that libjpeg refuses by rule. Used by tests/test_jpeg_corpus.py (ASan/UBSan harness + the Pillow equivalence rule).
 """
 from __future__ import annotations
 
@@ -182,6 +183,11 @@ def corpus():
         out.append((f"{name}:valid", d))
         out += structured(name, d)
         out += mutated(name, d, 1000 + i)
+    # hand-built streams no mutation of a Pillow file reaches, all refused by libjpeg: interleaved MCUs of 12 blocks,
+    # scans that name the frame's components out of order, an all-ones Huffman code
+    from jpeg_stream_writer import refused_cases
+
+    out += [(f"written:{lab}", d) for lab, d in refused_cases()]
     return out
 
 

@@ -20,7 +20,9 @@ algorithms for that configuration, restated:
   * jcmarker.c: SOI, JFIF APP0 (1.01, density 0 / 1:1), [COM], DQT per table, SOF0, DHT per table in scan
     order, SOS, EOI.
 tests/test_jpeg_enc.py pins this restatement against Pillow's own output byte for byte; the GPU encoder
-(spotter_amd/csrc/jpeg_enc.hip + jpeg_host.h) is then checked against both.
+(spotter_amd/csrc/jpeg_enc.hip + jpeg_host.h) is then checked against both. scan_order_blocks, mcu_bit_counts and
+entropy_bits(stuff=False) are the exact expectation of each of its stages (tests/test_gpu_jpeg_enc_stages.py);
+symbol_histogram tells which parts of the entropy coder a set of inputs reaches.
 """
 from __future__ import annotations
 
@@ -267,44 +269,106 @@ class _BitWriter:
         self.acc, self.n = 0, 0
 
 
-def entropy_bits(comps, stuff=True):
-    """The scan's entropy-coded segment (stuffed, padded) for the interleaved baseline scan; stuff=False: the raw
-    code stream (no stuffing, last partial byte zero-filled) and its bit count, the GPU encoder's output form."""
-    tabs = [(_derive(DC_LUM), _derive(AC_LUM)), (_derive(DC_CHR), _derive(AC_CHR))]
-    w = _BitWriter(stuff)
+def _huff_tables():
+    return [(_derive(DC_LUM), _derive(AC_LUM)), (_derive(DC_CHR), _derive(AC_CHR))]
+
+
+def _encode_block(b, last, dc, ac):
+    """jchuff.c encode_one_block on one natural-order block against the previous DC `last`: the (code, size) pairs
+    in stream order, the DC-difference size, the AC symbols as (run mod 16, size), the number of ZRL codes, and
+    whether an EOB was written."""
+    codes = []
+    diff = int(b[0]) - last
+    t, t2 = (-diff, diff - 1) if diff < 0 else (diff, diff)
+    dc_size = t.bit_length()
+    codes.append(dc[dc_size])
+    if dc_size:
+        codes.append((t2, dc_size))
+    syms, zrl, prev = [], 0, 0
+    zz = b[NATURAL]
+    for k in np.flatnonzero(zz[1:]) + 1:
+        k = int(k)
+        r = k - prev - 1
+        prev = k
+        while r > 15:
+            codes.append(ac[0xF0])
+            zrl += 1
+            r -= 16
+        x = int(zz[k])
+        t, t2 = (-x, x - 1) if x < 0 else (x, x)
+        nb = t.bit_length()
+        codes.append(ac[(r << 4) + nb])
+        codes.append((t2, nb))
+        syms.append((r, nb))
+    eob = prev < 63
+    if eob:
+        codes.append(ac[0x00])
+    return codes, dc_size, syms, zrl, eob
+
+
+def _walk_scan(comps):
+    """The interleaved baseline scan in stream order: yields (mcu index, table class 0 luma / 1 chroma,
+    _encode_block's tuple) per block, carrying each component's DC prediction."""
+    tabs = _huff_tables()
     last = [0] * len(comps)
     mcuy = comps[0][0].shape[0] // comps[0][2]
     mcux = comps[0][0].shape[1] // comps[0][1]
     for my in range(mcuy):
         for mx in range(mcux):
             for c, (blocks, h, v) in enumerate(comps):
-                dc, ac = tabs[0 if c == 0 else 1]
+                cls = 0 if c == 0 else 1
+                dc, ac = tabs[cls]
                 for yy in range(v):
                     for xx in range(h):
                         b = blocks[my * v + yy, mx * h + xx]
-                        diff = int(b[0]) - last[c]
+                        yield my * mcux + mx, cls, _encode_block(b, last[c], dc, ac)
                         last[c] = int(b[0])
-                        t, t2 = (-diff, diff - 1) if diff < 0 else (diff, diff)
-                        nb = t.bit_length()
-                        w.put(*dc[nb])
-                        if nb:
-                            w.put(t2, nb)
-                        r = 0
-                        for k in range(1, 64):
-                            x = int(b[NATURAL[k]])
-                            if x == 0:
-                                r += 1
-                                continue
-                            while r > 15:
-                                w.put(*ac[0xF0])
-                                r -= 16
-                            t, t2 = (-x, x - 1) if x < 0 else (x, x)
-                            nb = t.bit_length()
-                            w.put(*ac[(r << 4) + nb])
-                            w.put(t2, nb)
-                            r = 0
-                        if r > 0:
-                            w.put(*ac[0x00])
+
+
+def scan_order_blocks(comps):
+    """coefficient_blocks' components -> int16 [nmcu * blocks per MCU, 64]: the quantised coefficients in the order
+    the scan codes them (MCUs in raster order; within an MCU the luma blocks row-major, then Cb, then Cr), each
+    block in zig-zag order. The GPU encoder keeps its coefficients in exactly this layout."""
+    per = []
+    for blocks, h, v in comps:
+        mcuy, mcux = blocks.shape[0] // v, blocks.shape[1] // h
+        per.append(blocks.reshape(mcuy, v, mcux, h, 64).transpose(0, 2, 1, 3, 4).reshape(mcuy * mcux, v * h, 64))
+    return np.concatenate(per, axis=1)[..., NATURAL].reshape(-1, 64).astype(np.int16)
+
+
+def mcu_bit_counts(comps):
+    """int64 [nmcu]: the Huffman-coded length of every MCU (codes and magnitude bits, no stuffing, no padding)."""
+    nmcu = (comps[0][0].shape[0] // comps[0][2]) * (comps[0][0].shape[1] // comps[0][1])
+    out = np.zeros(nmcu, np.int64)
+    for mcu, _, (codes, *_rest) in _walk_scan(comps):
+        out[mcu] += sum(size for _, size in codes)
+    return out
+
+
+def symbol_histogram(comps):
+    """Which parts of the entropy coder a scan reaches. {"luma": t, "chroma": t, "mcu_bits": (shortest, longest)}
+    with t = {"ac": {(run mod 16, size)} of the AC symbols coded, "dc": {DC-difference sizes}, "zrl": {ZRL codes
+    per block, over the blocks that have any}, "max_zrl": the largest of them (0: none), "no_eob": a block whose
+    63rd coefficient is non-zero occurs}."""
+    t = [{"ac": set(), "dc": set(), "zrl": set(), "max_zrl": 0, "no_eob": False} for _ in range(2)]
+    for _, cls, (_codes, dc_size, syms, zrl, eob) in _walk_scan(comps):
+        t[cls]["ac"].update(syms)
+        t[cls]["dc"].add(dc_size)
+        if zrl:
+            t[cls]["zrl"].add(zrl)
+            t[cls]["max_zrl"] = max(t[cls]["max_zrl"], zrl)
+        t[cls]["no_eob"] |= not eob
+    n = mcu_bit_counts(comps)
+    return {"luma": t[0], "chroma": t[1], "mcu_bits": (int(n.min()), int(n.max()))}
+
+
+def entropy_bits(comps, stuff=True):
+    """The scan's entropy-coded segment (stuffed, padded) for the interleaved baseline scan; stuff=False: the raw
+    code stream (no stuffing, last partial byte zero-filled) and its bit count, the GPU encoder's output form."""
+    w = _BitWriter(stuff)
+    for _, _, (codes, *_rest) in _walk_scan(comps):
+        for code, size in codes:
+            w.put(code, size)
     if not stuff:
         n = w.total
         if w.n:

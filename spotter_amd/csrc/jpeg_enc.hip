@@ -10,12 +10,16 @@
 //   jpeg_scan_kernel    one workgroup: exclusive prefix sum of the MCU lengths → each MCU's bit offset; the
 //                       total; zeroes the words the segment will occupy.
 //   jpeg_emit_kernel    one thread per MCU: the same walk again, writing its codes at its offset (32-bit
-//                       atomic ORs; only the first and last word of an MCU are shared with its neighbours).
+//                       atomic ORs; an MCU shares its first and last word with its neighbours, and a word holds
+//                       several whole MCUs where they are short: a flat 4:4:4 MCU is 14 bits).
 //
 // The host (jpeg_host.h enc_finish) adds the markers, the 0xFF byte stuffing and the final 1-bit padding. The
 // Huffman tables are the Annex K.3 ones libjpeg uses without optimize_coding, derived at compile time from the
 // same arrays the DHT markers are written from. oracle/jpeg_enc_np.py restates the whole path and pins it
-// against Pillow's own output; tests/test_gpu_jpeg.py checks this file's bytes against both.
+// against Pillow's own output; tests/test_gpu_jpeg.py checks this file's bytes against both, and
+// tests/test_gpu_jpeg_enc_stages.py reads every stage's output off the workspace (coefficients, per-MCU bit
+// counts, offsets and total, the raw code stream) and compares it exactly with the oracle's, on inputs chosen for
+// the block, MCU-count and entropy-walk edges (tests/jpeg_enc_cases.py).
 #include "common.h"
 #include "jpeg_host.h"
 

@@ -5,7 +5,8 @@
    the reference's own test_pic.jpg decoded. That pins the oracle.
 2. The library's host half (sp_jpeg_enc_plan + sp_jpeg_enc_finish: layout, quantisation tables, reciprocals,
    markers, 0xFF stuffing, padding), fed the oracle's raw code stream, writes the same bytes. The GPU half
-   (the kernels) is checked against Pillow in tests/test_gpu_jpeg.py.
+   (the kernels) is checked against Pillow in tests/test_gpu_jpeg.py, and stage by stage against this oracle in
+   tests/test_gpu_jpeg_enc_stages.py (inputs: tests/jpeg_enc_cases.py, their premises: tests/test_jpeg_enc_cases.py).
 3. The rule that decides which save() calls take the GPU encoder.
 """
 import ctypes as C

@@ -97,27 +97,87 @@ def _buf(data):
     return a.ctypes.data, a.size, a
 
 
+def _error(rc, fn, msg=None):
+    """The exception for a non-zero return code of the library's `fn`: UnsupportedJpeg for SP_JPEG_UNSUPPORTED, else
+    RuntimeError("fn: <last error>"). msg: the error text as read on the thread that made the call (sp_last_error is
+    thread-local); None reads it here, on the calling thread."""
+    text = (lib().sp_last_error() if msg is None else msg).decode(errors="replace")
+    return UnsupportedJpeg(text) if rc == SP_JPEG_UNSUPPORTED else RuntimeError(f"{fn}: {text}")
+
+
+def _check(rc, fn):
+    if rc:
+        raise _error(rc, fn)
+
+
+def _parse(L, ptr, n) -> SpJpegLayout:
+    """The header pass: the layout of a file the library decodes, before anything is allocated for it. Raises
+    UnsupportedJpeg for a file the parser refuses and for one beyond Pillow's pixel limit."""
+    lay = SpJpegLayout()
+    _check(L.sp_jpeg_decode_coefs(ptr, n, C.byref(lay), None, 0), "sp_jpeg_decode_coefs")
+    _check_pixels(lay)
+    return lay
+
+
+def _pack(L, ptr, n, buf, alloc):
+    """sp_jpeg_entropy_pack into `buf`, the buffer that is offered first (a uint8 numpy array or tensor, or None),
+    and, when that is too small (SP_JPEG_PKG_SMALL: the packer has filled in the layout and the package's size), a
+    second pass into alloc(layout, scan): (return code, layout, scan, the buffer that holds the package)."""
+    lay, scan = SpJpegLayout(), SpJpegScan()
+
+    def run(b):
+        if b is None:
+            return L.sp_jpeg_entropy_pack(ptr, n, C.byref(lay), C.byref(scan), None, 0)
+        p, size = (b.data_ptr(), b.numel()) if torch.is_tensor(b) else (b.ctypes.data, b.size)
+        return L.sp_jpeg_entropy_pack(ptr, n, C.byref(lay), C.byref(scan), p, size)
+
+    rc = run(buf)
+    if rc == SP_JPEG_PKG_SMALL:
+        buf = alloc(lay, scan)
+        rc = run(buf)
+    return rc, lay, scan, buf
+
+
+def _greedy(needs, caps) -> int:
+    """The greedy chunk rule: how many leading entries of `needs` (one tuple of sizes per file, a size per budget in
+    `caps`) form the next chunk. As many as fit every budget, SP_JPEG_BATCH_MAX at the most, and one at the least: a
+    file beyond a budget runs as a chunk of its own."""
+    n, tot = 0, [0] * len(caps)
+    for need in needs:
+        if n and (n == SP_JPEG_BATCH_MAX or any(t + x > cap for t, x, cap in zip(tot, need, caps))):
+            break
+        n += 1
+        tot = [t + x for t, x in zip(tot, need)]
+    return n
+
+
+def _empty(n, dtype, device):
+    """n uninitialised elements on `device`, or in pinned host memory when device is None."""
+    if device is None:
+        return torch.empty(n, dtype=dtype, pin_memory=True)
+    return torch.empty(n, dtype=dtype, device=device)
+
+
+def _grow(t, n, dtype, device=None, cap=None):
+    """t when it holds n elements, else a new buffer (pinned host memory when device is None) of n elements, 1 Mi
+    at the least and, where a cap is given (n is within it), `cap` at the most."""
+    if t is not None and t.numel() >= n:
+        return t
+    n = max(n, 1 << 20)
+    return _empty(n if cap is None else min(cap, n), dtype, device)
+
+
 def decode_coefs(data, out: np.ndarray | None = None):
     """Host entropy decode: (layout, int16 coefficients [total_blocks, 64] natural order). out: reuse this
     int16 buffer (e.g. a pinned one) when it is large enough."""
     ptr, n, keep = _buf(data)
-    lay = SpJpegLayout()
     L = lib()
-    rc = L.sp_jpeg_decode_coefs(ptr, n, C.byref(lay), None, 0)
-    if rc == SP_JPEG_UNSUPPORTED:
-        raise UnsupportedJpeg(L.sp_last_error().decode(errors="replace"))
-    if rc:
-        raise RuntimeError(f"sp_jpeg_decode_coefs: {L.sp_last_error().decode(errors='replace')}")
-    _check_pixels(lay)
+    lay = _parse(L, ptr, n)
     need = lay.total_blocks * 64
     if out is None or out.size < need:
         out = np.empty(need, dtype=np.int16)
-    rc = L.sp_jpeg_decode_coefs(ptr, n, C.byref(lay), out.ctypes.data, out.size)
+    _check(L.sp_jpeg_decode_coefs(ptr, n, C.byref(lay), out.ctypes.data, out.size), "sp_jpeg_decode_coefs")
     del keep
-    if rc == SP_JPEG_UNSUPPORTED:
-        raise UnsupportedJpeg(L.sp_last_error().decode(errors="replace"))
-    if rc:
-        raise RuntimeError(f"sp_jpeg_decode_coefs: {L.sp_last_error().decode(errors='replace')}")
     return lay, out[:need].reshape(-1, 64)
 
 
@@ -126,21 +186,16 @@ def pack_scan(data):
     eligible (progressive, multi-scan, irregular restarts: it keeps the host entropy decode). Raises
     UnsupportedJpeg where the host parser refuses the file. No device call."""
     ptr, n, keep = _buf(data)
-    lay, scan = SpJpegLayout(), SpJpegScan()
-    L = lib()
-    rc = L.sp_jpeg_entropy_pack(ptr, n, C.byref(lay), C.byref(scan), None, 0)
-    pkg = None
-    if rc == SP_JPEG_PKG_SMALL:
+
+    def alloc(lay, scan):
         _check_pixels(lay)
-        pkg = np.zeros(scan.pkg_bytes, dtype=np.uint8)
-        rc = L.sp_jpeg_entropy_pack(ptr, n, C.byref(lay), C.byref(scan), pkg.ctypes.data, pkg.size)
+        return np.zeros(scan.pkg_bytes, dtype=np.uint8)
+
+    rc, lay, scan, pkg = _pack(lib(), ptr, n, None, alloc)
     del keep
-    if rc == SP_JPEG_UNSUPPORTED:
-        raise UnsupportedJpeg(L.sp_last_error().decode(errors="replace"))
     if rc == SP_JPEG_NOT_ELIGIBLE:
         return None
-    if rc:
-        raise RuntimeError(f"sp_jpeg_entropy_pack: {L.sp_last_error().decode(errors='replace')}")
+    _check(rc, "sp_jpeg_entropy_pack")
     return lay, scan, pkg[:scan.pkg_bytes]
 
 
@@ -154,10 +209,8 @@ def emulate_entropy(data):
     lay, scan, pkg = packed
     co = np.empty(lay.total_blocks * 64, dtype=np.int16)
     status, rounds = C.c_int32(0), (C.c_int32 * 2)()
-    L = lib()
-    if L.sp_jpeg_entropy_emulate(pkg.ctypes.data, C.byref(scan), C.byref(lay), co.ctypes.data, co.size,
-                                 C.byref(status), rounds):
-        raise RuntimeError(f"sp_jpeg_entropy_emulate: {L.sp_last_error().decode(errors='replace')}")
+    _check(lib().sp_jpeg_entropy_emulate(pkg.ctypes.data, C.byref(scan), C.byref(lay), co.ctypes.data, co.size,
+                                         C.byref(status), rounds), "sp_jpeg_entropy_emulate")
     return lay, co.reshape(-1, 64), status.value, (rounds[0], rounds[1])
 
 
@@ -170,10 +223,36 @@ def layout_dict(lay: SpJpegLayout) -> dict:
     return d
 
 
+def _plan(L, lays):
+    """sp_jpeg_batch_plan over the layouts of one chunk: (layout array, table, totals)."""
+    n = len(lays)
+    arr, items, totals = (SpJpegLayout * n)(*lays), (SpJpegBatchItem * n)(), SpJpegBatchTotals()
+    _check(L.sp_jpeg_batch_plan(arr, n, items, C.byref(totals)), "sp_jpeg_batch_plan")
+    return arr, items, totals
+
+
+def _chunk_need(lay):
+    """What a file adds to a decode_many chunk: (int16 coefficients, plane bytes, RGB arena bytes), the budgets being
+    KEEP_COEFS, KEEP_WORK and KEEP_ARENA."""
+    return lay.total_blocks * 64, _a16(lay.plane_bytes), (3 * lay.width * lay.height + 255) & ~255
+
+
+def _view(arena, it):
+    """Image `it` (a table row) of a chunk's RGB arena, as decode() returns it."""
+    H, W = it.lay.height, it.lay.width
+    return arena[it.rgb_off:it.rgb_off + H * W * 3].view(H, W, 3)
+
+
+_OUTSIDE = ("coefficients outside the IDCT range shared with libjpeg-turbo's SIMD code (corrupt or crafted data): "
+            "left to Pillow")
+
+
 class JpegDecoder:
-    """Per-device decoder state: a pinned host coefficient buffer and device buffers, grown as needed up to
-    KEEP_COEFS / KEEP_WORK and reused (one decode at a time per decoder; the lock serialises concurrent
-    callers). A larger image decodes through buffers allocated for that call and released after it.
+    """Per-device decoder state: pinned staging and device buffers, grown as needed up to KEEP_COEFS / KEEP_WORK /
+    KEEP_PKG and reused (one decode at a time per decoder; the lock serialises concurrent callers). A larger image
+    decodes through buffers allocated for that call and released after it. The four decode forms (one file or a
+    chunk, host or GPU entropy) get their buffers from one store (_take) and reach the device through one method
+    (_submit), which keeps the event discipline.
 
     entropy: where the Huffman decode of baseline files runs. "host" (default): sp_jpeg_decode_coefs, the
     coefficients go up. "gpu" / "auto": the host only parses the headers and packs the scan (sp_jpeg_entropy_pack,
@@ -186,95 +265,146 @@ class JpegDecoder:
         self.dev = torch.device(device)
         self.entropy = check_jpeg_entropy(entropy)
         self.stats = {"gpu": 0, "host": 0, "fallback": {}, "h2d_bytes": 0}
-        self._g: dict = {}  # entropy="gpu" buffers: pinned "pkg_host", device "pkg", "ent", "coefs", "work"
+        self.batch_stats = _new_batch_stats()  # decode_many's counters
         self._lock = threading.Lock()
-        self._host = None  # pinned int16
-        self._coefs = None  # device int16
-        self._work = None  # device uint8 planes
-        self._copied = None  # event: the last H2D copy out of the pinned buffer is done
-        self._done = None  # event: the last decode's kernels are done with the device buffers
-        self._status = torch.zeros(1, dtype=torch.int32, device=self.dev)  # sp_jpeg_to_rgb's envelope flag
-        self._status_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
-        # decode_many: one status word per image of a chunk, the counters, the entropy-decode pool
-        self._bstatus = torch.zeros(SP_JPEG_BATCH_MAX, dtype=torch.int32, device=self.dev)
-        self._bstatus_host = torch.zeros(SP_JPEG_BATCH_MAX, dtype=torch.int32, pin_memory=True)
-        self.batch_stats = _new_batch_stats()
-        self._workers = None
+        # The kept buffers by name (_take). Host entropy: the pinned int16 "coefs_host", its device copy "coefs_up"
+        # (a chunk's table travels behind the coefficients) and the planes "work_up". GPU entropy: the pinned
+        # "pkg_host", its device copy "pkg", the entropy workspace "ent", the coefficients the launch chain writes
+        # "coefs" and the planes "work". The two paths keep separate coefficients and planes: a file that falls back
+        # to the host path within one call leaves what the GPU chain wrote in place.
+        self._kept: dict = {}
+        self._copied = None  # event: the last H2D copy out of a kept pinned buffer is done
+        self._done = None  # event: the last run's kernels are done with the kept device buffers
+        # one status word per image of a chunk (decode() uses the first: sp_jpeg_to_rgb's envelope flag)
+        self._status = torch.zeros(SP_JPEG_BATCH_MAX, dtype=torch.int32, device=self.dev)
+        self._status_host = torch.zeros(SP_JPEG_BATCH_MAX, dtype=torch.int32, pin_memory=True)
+        self._workers = None  # decode_many's entropy-decode pool
 
-    def _buffers(self, n_coef, n_work):
-        """(pinned host coefficients, device coefficients, device planes, kept?) for one decode."""
-        if n_coef > KEEP_COEFS or n_work > KEEP_WORK:
-            if self._copied is not None:
-                self._copied.synchronize()
-            return (torch.empty(n_coef, dtype=torch.int16, pin_memory=True),
-                    torch.empty(n_coef, dtype=torch.int16, device=self.dev),
-                    torch.empty(n_work, dtype=torch.uint8, device=self.dev), False)
-        grow_c = self._host is None or self._host.numel() < n_coef
-        grow_w = self._work is None or self._work.numel() < n_work
-        if (grow_c or grow_w) and self._done is not None:
-            # the old buffers may still be read by the previous decode on another stream: let it finish
-            # before they go back to the caching allocator
+    # The names the GPU tests read the device coefficients by after a call: the store itself (`_g["coefs"]`, what the
+    # GPU chain wrote) and the host path's uploaded coefficients. Read-only views of `_kept`; nothing here uses them.
+    _g = property(lambda self: self._kept)
+    _coefs = property(lambda self: self._kept.get("coefs_up"))
+
+    def _take(self, need):
+        """The buffers of one run. need: {name: (elements, cap, dtype, device, or None for pinned host memory)};
+        returns ({name: buffer}, kept?). All sizes within their caps: the kept buffers, each grown to
+        min(cap, max(elements, 1 Mi)) when too small (0 elements ask for whatever is kept, None included). Any size
+        beyond its cap: buffers of this call, and the kept ones stay as they are. The pinned buffers are handed out
+        once the last copy out of them is done, so the caller may fill them at once."""
+        if self._copied is not None:
+            self._copied.synchronize()  # the pinned buffer is free again
+        if any(n > cap for n, cap, _, _ in need.values()):
+            return {k: _empty(max(n, 16), dtype, device) for k, (n, _, dtype, device) in need.items()}, False
+        kept = self._kept
+        small = [k for k, (n, _, _, _) in need.items() if n > (kept[k].numel() if k in kept else 0)]
+        if small and self._done is not None:
+            # the old buffers may still be read by the previous decode on another stream: let it finish before they
+            # go back to the caching allocator
             self._done.synchronize()
-        if grow_c:
-            n = min(KEEP_COEFS, max(n_coef, 1 << 20))
-            self._host = torch.empty(n, dtype=torch.int16, pin_memory=True)
-            self._coefs = torch.empty(n, dtype=torch.int16, device=self.dev)
-        if grow_w:
-            self._work = torch.empty(min(KEEP_WORK, max(n_work, 1 << 20)), dtype=torch.uint8, device=self.dev)
-        return self._host, self._coefs, self._work, True
+        for k in small:
+            n, cap, dtype, device = need[k]
+            kept[k] = _grow(kept.get(k), n, dtype, device, cap)
+        return {k: kept.get(k) for k in need}, True
+
+    def _submit(self, kept, src, dst, n, nstatus, launch):
+        """One run on torch's current stream: copy src[:n] (a pinned buffer of _take, filled by the caller) to
+        dst[:n], zero `nstatus` status words, launch(status pointer, stream) (it raises where a launch is refused),
+        read the status words back and wait: the list of status words. kept: the buffers are _take's kept ones, so
+        the run is fenced behind the previous one and leaves its two events for the next. The run returns, or
+        raises, only after everything it enqueued is done, so the buffers never change hands with work in flight."""
+        cur = torch.cuda.current_stream(self.dev)
+        if kept and self._done is not None:
+            cur.wait_event(self._done)  # another stream's previous decode may still read the buffers
+        copied, done = torch.cuda.Event(), torch.cuda.Event()
+        status = self._status[:nstatus]
+        try:
+            dst[:n].copy_(src[:n], non_blocking=True)
+            copied.record(cur)
+            status.zero_()
+            launch(status.data_ptr(), cur.cuda_stream)
+            self._status_host[:nstatus].copy_(status, non_blocking=True)
+        finally:
+            done.record(cur)
+            done.synchronize()
+            if kept:
+                self._copied, self._done = copied, done
+        return self._status_host[:nstatus].tolist()
 
     def decode(self, data, out: torch.Tensor | None = None) -> torch.Tensor:
         """JPEG bytes → uint8 [H, W, 3] on the device (on torch's current stream). Returns once the kernels
         have run (the IDCT's envelope flag is read back: a file outside it raises UnsupportedJpeg, for Pillow)."""
         ptr, n, keep = _buf(data)
-        lay = SpJpegLayout()
         L = lib()
         with self._lock:
             if self.entropy != "host":
                 got = self._decode_gpu_entropy(L, ptr, n, out)
                 if got is not None:
                     return got
-            rc = L.sp_jpeg_decode_coefs(ptr, n, C.byref(lay), None, 0)
-            if rc == SP_JPEG_UNSUPPORTED:
-                raise UnsupportedJpeg(L.sp_last_error().decode(errors="replace"))
-            if rc:
-                raise RuntimeError(f"sp_jpeg_decode_coefs: {L.sp_last_error().decode(errors='replace')}")
-            _check_pixels(lay)
+            lay = _parse(L, ptr, n)
             ncoef = lay.total_blocks * 64
-            host, coefs, work, kept = self._buffers(ncoef, lay.plane_bytes)
-            if kept and self._copied is not None:
-                self._copied.synchronize()  # the pinned buffer is free again
-            rc = L.sp_jpeg_decode_coefs(ptr, n, C.byref(lay), host.data_ptr(), host.numel())
+            b, kept = self._take({"coefs_host": (ncoef, KEEP_COEFS, torch.int16, None),
+                                  "coefs_up": (ncoef, KEEP_COEFS, torch.int16, self.dev),
+                                  "work_up": (lay.plane_bytes, KEEP_WORK, torch.uint8, self.dev)})
+            host = b["coefs_host"]
+            _check(L.sp_jpeg_decode_coefs(ptr, n, C.byref(lay), host.data_ptr(), host.numel()), "sp_jpeg_decode_coefs")
             del keep
-            if rc == SP_JPEG_UNSUPPORTED:
-                raise UnsupportedJpeg(L.sp_last_error().decode(errors="replace"))
-            if rc:
-                raise RuntimeError(f"sp_jpeg_decode_coefs: {L.sp_last_error().decode(errors='replace')}")
-            cur = torch.cuda.current_stream(self.dev)
-            if kept and self._done is not None:
-                cur.wait_event(self._done)  # another stream's previous decode may still read the buffers
-            coefs[:ncoef].copy_(host[:ncoef], non_blocking=True)
-            copied = torch.cuda.Event()
-            copied.record()
-            H, W = lay.height, lay.width
-            if out is None:
-                out = torch.empty((H, W, 3), dtype=torch.uint8, device=self.dev)
-            assert out.dtype == torch.uint8 and out.is_cuda and out.shape == (H, W, 3) and out.is_contiguous()
-            self._status.zero_()
-            rc = L.sp_jpeg_to_rgb(coefs.data_ptr(), C.byref(lay), work.data_ptr(), work.numel(),
-                                  out.data_ptr(), W * 3, self._status.data_ptr(), cur.cuda_stream)
-            if rc:
-                raise RuntimeError(f"sp_jpeg_to_rgb: {L.sp_last_error().decode(errors='replace')}")
-            self._status_host.copy_(self._status, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(cur)
-            done.synchronize()
-            if kept:
-                self._copied, self._done = copied, done
-            if int(self._status_host[0]):
-                raise UnsupportedJpeg("coefficients outside the IDCT range shared with libjpeg-turbo's SIMD "
-                                      "code (corrupt or crafted data): left to Pillow")
+            out, flag = self._to_rgb(L, lay, out, kept, host, b["coefs_up"], ncoef, b["coefs_up"], b["work_up"])
+            if flag:
+                raise UnsupportedJpeg(_OUTSIDE)
             return out
+
+    def _decode_gpu_entropy(self, L, ptr, n, out):
+        """entropy="gpu": pack on the host into the reused pinned buffer, copy the package asynchronously, run the
+        entropy kernels and sp_jpeg_to_rgb, one status readback. The image, or None when the file takes the host path
+        (not eligible, or a non-zero status word); raises UnsupportedJpeg as the host parser does. Lock held."""
+        def pinned(nbytes):
+            return self._take({"pkg_host": (nbytes, KEEP_PKG, torch.uint8, None)})[0]["pkg_host"]
+
+        def alloc(lay, scan):
+            _check_pixels(lay)
+            return pinned(scan.pkg_bytes)
+
+        # the first pass goes into whatever pinned buffer is kept: a file that fits costs one pass
+        rc, lay, scan, host = _pack(L, ptr, n, pinned(0), alloc)
+        if rc == SP_JPEG_NOT_ELIGIBLE:
+            self.stats["host"] += 1
+            return None
+        _check(rc, "sp_jpeg_entropy_pack")
+        _check_pixels(lay)
+        ncoef = lay.total_blocks * 64
+        # (a package beyond KEEP_PKG is in a pinned buffer of this call, and "pkg" is then beyond it too)
+        b, kept = self._take({"pkg": (scan.pkg_bytes, KEEP_PKG, torch.uint8, self.dev),
+                              "ent": (scan.work_bytes, KEEP_PKG, torch.uint8, self.dev),
+                              "coefs": (ncoef, KEEP_COEFS, torch.int16, self.dev),
+                              "work": (lay.plane_bytes, KEEP_WORK, torch.uint8, self.dev)})
+        out, flag = self._to_rgb(L, lay, out, kept, host, b["pkg"], scan.pkg_bytes, b["coefs"], b["work"],
+                                 entropy=(scan, b["ent"]))
+        self.stats["h2d_bytes"] += int(scan.pkg_bytes)
+        if flag:  # the GPU result is discarded; the host path accepts the file or raises UnsupportedJpeg by its own rules
+            self.stats["fallback"][flag] = self.stats["fallback"].get(flag, 0) + 1
+            return None
+        self.stats["gpu"] += 1
+        return out
+
+    def _to_rgb(self, L, lay, out, kept, src, dst, n, coefs, work, entropy=None):
+        """The back half of decode(): (image, status word). src[:n] goes up to dst[:n]: the coefficients themselves
+        (dst is coefs), or, with entropy = (scan, workspace), the scan package, from which sp_jpeg_entropy_decode
+        writes coefs on the device; then sp_jpeg_to_rgb into `out` (allocated here when None)."""
+        H, W = lay.height, lay.width
+        if out is None:
+            out = torch.empty((H, W, 3), dtype=torch.uint8, device=self.dev)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.shape == (H, W, 3) and out.is_contiguous()
+
+        def launch(status, stream):
+            if entropy is not None:
+                scan, ent = entropy
+                _check(L.sp_jpeg_entropy_decode(dst.data_ptr(), C.byref(scan), C.byref(lay), ent.data_ptr(),
+                                                ent.numel(), coefs.data_ptr(), coefs.numel(), status, stream),
+                       "sp_jpeg_entropy_decode")
+            _check(L.sp_jpeg_to_rgb(coefs.data_ptr(), C.byref(lay), work.data_ptr(), work.numel(), out.data_ptr(),
+                                    W * 3, status, stream), "sp_jpeg_to_rgb")
+
+        return out, self._submit(kept, src, dst, n, 1, launch)[0]
 
     def decode_many(self, datas, max_workers=None) -> list:
         """Many JPEGs → one entry per input, in input order: the uint8 [H, W, 3] device tensor decode() returns for
@@ -308,19 +438,10 @@ class JpegDecoder:
         out: list = [None] * len(bufs)
         lays: list = [None] * len(bufs)
         for i, (ptr, n, _) in enumerate(bufs):
-            lay = SpJpegLayout()
-            rc = L.sp_jpeg_decode_coefs(ptr, n, C.byref(lay), None, 0)
-            if rc == SP_JPEG_UNSUPPORTED:
-                out[i] = UnsupportedJpeg(L.sp_last_error().decode(errors="replace"))
-                continue
-            if rc:
-                raise RuntimeError(f"sp_jpeg_decode_coefs: {L.sp_last_error().decode(errors='replace')}")
             try:
-                _check_pixels(lay)
+                lays[i] = _parse(L, ptr, n)
             except UnsupportedJpeg as e:
                 out[i] = e
-                continue
-            lays[i] = lay
         workers = max_workers if max_workers is not None else default_decode_workers()
         if workers < 1:
             raise ValueError("max_workers must be at least 1")
@@ -328,43 +449,30 @@ class JpegDecoder:
         if self.entropy != "host":
             # the GPU-entropy chunks first; what they decoded leaves `lays`, the rest takes the host chunks below
             self._decode_many_gpu_entropy(L, bufs, lays, out, workers)
-        # greedy chunks in input order, by count and by the three buffer budgets
-        chunks, cur_chunk, tot = [], [], [0, 0, 0]
-        for i, lay in enumerate(lays):
-            if lay is None:
-                continue
-            need = (lay.total_blocks * 64, (lay.plane_bytes + 15) & ~15, (3 * lay.width * lay.height + 255) & ~255)
-            if cur_chunk and (len(cur_chunk) == SP_JPEG_BATCH_MAX or tot[0] + need[0] + _TABLE_ELEMS > KEEP_COEFS
-                              or tot[1] + need[1] > KEEP_WORK or tot[2] + need[2] > KEEP_ARENA):
-                chunks.append(cur_chunk)
-                cur_chunk, tot = [], [0, 0, 0]
-            cur_chunk.append(i)
-            tot = [a + b for a, b in zip(tot, need)]
-        if cur_chunk:
-            chunks.append(cur_chunk)
+        live = [i for i, lay in enumerate(lays) if lay is not None]
+        needs = [_chunk_need(lays[i]) for i in live]
+        caps = (KEEP_COEFS - _TABLE_ELEMS, KEEP_WORK, KEEP_ARENA)  # the table travels behind the coefficients
         st = self.batch_stats
         with self._lock:
             st["calls"] += 1
             st["refused"] += refused
-            for idx in chunks:
-                self._decode_chunk(L, idx, bufs, lays, out, workers)
+            pos = 0
+            while pos < len(live):  # greedy chunks in input order
+                n = _greedy(needs[pos:pos + SP_JPEG_BATCH_MAX], caps)
+                self._decode_chunk(L, live[pos:pos + n], bufs, lays, out, workers)
+                pos += n
         return out
 
     def _decode_chunk(self, L, idx, bufs, lays, out, workers):
-        """One chunk of decode_many (lock held): out[i] for i in idx."""
+        """One host-entropy chunk of decode_many (lock held): out[i] for i in idx."""
         n = len(idx)
-        arr = (SpJpegLayout * n)(*[lays[i] for i in idx])
-        items = (SpJpegBatchItem * n)()
-        totals = SpJpegBatchTotals()
-        if L.sp_jpeg_batch_plan(arr, n, items, C.byref(totals)):
-            raise RuntimeError(f"sp_jpeg_batch_plan: {L.sp_last_error().decode(errors='replace')}")
+        _, items, totals = _plan(L, [lays[i] for i in idx])
         tab_off = (totals.coef_elems + 7) & ~7  # the table follows the coefficients, 16-byte aligned
-        tab_bytes = C.sizeof(items)
-        nelem = tab_off + (tab_bytes + 1) // 2
-        host, coefs, work, kept = self._buffers(nelem, totals.work_bytes)
-        if kept and self._copied is not None:
-            self._copied.synchronize()  # the pinned buffer is free again
-        hp = host.data_ptr()
+        nelem = tab_off + (C.sizeof(items) + 1) // 2
+        b, kept = self._take({"coefs_host": (nelem, KEEP_COEFS, torch.int16, None),
+                              "coefs_up": (nelem, KEEP_COEFS, torch.int16, self.dev),
+                              "work_up": (totals.work_bytes, KEEP_WORK, torch.uint8, self.dev)})
+        hp = b["coefs_host"].data_ptr()
 
         def entropy(k):
             ptr, nb, _ = bufs[idx[k]]
@@ -373,7 +481,7 @@ class JpegDecoder:
                                         lays[idx[k]].total_blocks * 64)
             if rc == 0:
                 items[k].lay.quant = lay.quant  # the tables as latched at each component's first scan
-            return rc, L.sp_last_error()
+            return rc, L.sp_last_error()  # (thread-local: read on the thread that made the call)
 
         if workers > 1 and n > 1:
             rcs = list(self._pool(workers).map(entropy, range(n)))
@@ -381,34 +489,15 @@ class JpegDecoder:
             rcs = [entropy(k) for k in range(n)]
         bad = {}
         for k, (rc, msg) in enumerate(rcs):
-            if rc == SP_JPEG_UNSUPPORTED:
-                # its slice holds whatever the decoder wrote before it stopped: the kernels run over it (any int16
-                # is a valid input) and the result is dropped
-                bad[k] = UnsupportedJpeg(msg.decode(errors="replace"))
-            elif rc:
-                raise RuntimeError(f"sp_jpeg_decode_coefs: {msg.decode(errors='replace')}")
-        C.memmove(hp + 2 * tab_off, items, tab_bytes)
-        cur = torch.cuda.current_stream(self.dev)
-        if kept and self._done is not None:
-            cur.wait_event(self._done)  # another stream's previous decode may still read the buffers
-        coefs[:nelem].copy_(host[:nelem], non_blocking=True)
-        copied = torch.cuda.Event()
-        copied.record()
-        arena = torch.empty(totals.rgb_bytes, dtype=torch.uint8, device=self.dev)
-        status = self._bstatus[:n]
-        status.zero_()
-        rc = L.sp_jpeg_batch_to_rgb(coefs.data_ptr(), totals.coef_elems, coefs.data_ptr() + 2 * tab_off, items, n,
-                                    C.byref(totals), work.data_ptr(), work.numel(), arena.data_ptr(), arena.numel(),
-                                    status.data_ptr(), cur.cuda_stream)
-        if rc:
-            raise RuntimeError(f"sp_jpeg_batch_to_rgb: {L.sp_last_error().decode(errors='replace')}")
-        self._bstatus_host[:n].copy_(status, non_blocking=True)
-        done = torch.cuda.Event()
-        done.record(cur)
-        done.synchronize()
-        if kept:
-            self._copied, self._done = copied, done
-        flags = self._bstatus_host[:n].tolist()
+            if rc:
+                # a refused file's slice holds whatever the decoder wrote before it stopped: the kernels run over it
+                # (any int16 is a valid input) and the result is dropped
+                bad[k] = _error(rc, "sp_jpeg_decode_coefs", msg)
+                if not isinstance(bad[k], UnsupportedJpeg):
+                    raise bad[k]
+        C.memmove(hp + 2 * tab_off, items, C.sizeof(items))
+        arena, flags = self._batch_to_rgb(L, items, totals, kept, b["coefs_host"], b["coefs_up"], nelem, 2 * tab_off,
+                                          b["coefs_up"], b["work_up"])
         st = self.batch_stats
         st["chunks"] += 1
         st["images"] += n
@@ -419,36 +508,46 @@ class JpegDecoder:
                 out[i] = bad[k]
             elif flags[k]:
                 st["flagged"] += 1
-                out[i] = UnsupportedJpeg("coefficients outside the IDCT range shared with libjpeg-turbo's SIMD "
-                                         "code (corrupt or crafted data): left to Pillow")
+                out[i] = UnsupportedJpeg(_OUTSIDE)
             else:
-                it = items[k]
-                H, W = it.lay.height, it.lay.width
-                out[i] = arena[it.rgb_off:it.rgb_off + H * W * 3].view(H, W, 3)
+                out[i] = _view(arena, items[k])
+
+    def _batch_to_rgb(self, L, items, totals, kept, src, dst, n, tab_off, coefs, work, entropy=None):
+        """The back half of a chunk: (RGB arena, status word per image). src[:n] goes up to dst[:n], the table at
+        byte tab_off of it: the coefficients themselves (dst is coefs), or, with entropy = (entropy table, its
+        totals, its byte offset in dst, workspace), the scan packages, from which sp_jpeg_entropy_batch_decode
+        writes coefs on the device; then sp_jpeg_batch_to_rgb into a new arena."""
+        cnt = len(items)
+        arena = torch.empty(totals.rgb_bytes, dtype=torch.uint8, device=self.dev)
+
+        def launch(status, stream):
+            if entropy is not None:
+                ent, etot, ent_off, ws = entropy
+                _check(L.sp_jpeg_entropy_batch_decode(dst.data_ptr(), etot.pkg_bytes, dst.data_ptr() + ent_off, ent,
+                                                      cnt, C.byref(etot), ws.data_ptr(), ws.numel(), coefs.data_ptr(),
+                                                      totals.coef_elems, status, stream),
+                       "sp_jpeg_entropy_batch_decode")
+            _check(L.sp_jpeg_batch_to_rgb(coefs.data_ptr(), totals.coef_elems, dst.data_ptr() + tab_off, items, cnt,
+                                          C.byref(totals), work.data_ptr(), work.numel(), arena.data_ptr(),
+                                          arena.numel(), status, stream), "sp_jpeg_batch_to_rgb")
+
+        return arena, self._submit(kept, src, dst, n, cnt, launch)
 
     def _decode_many_gpu_entropy(self, L, bufs, lays, out, workers):
         """decode_many on an entropy="gpu" decoder: pack the accepted files, a window of SP_JPEG_BATCH_MAX at a time,
         and run the eligible ones in GPU-entropy chunks as the windows fill them, so at most two windows' packages are
-        alive at once. out[i] is set and lays[i] cleared for every file the GPU chain decoded with status 0. The lock
-        is held throughout: the pool and the counters are the decoder's."""
+        alive at once. out[i] is set and lays[i] cleared for every file the GPU chain decoded with status 0. Takes the
+        lock itself and holds it throughout: the pool and the counters are the decoder's."""
         live = [i for i, lay in enumerate(lays) if lay is not None]
 
         def pack(i):
             ptr, nb, _ = bufs[i]
-            lay, scan = SpJpegLayout(), SpJpegScan()
             lay0 = lays[i]
             nmcu = (lay0.bw[0] // max(1, lay0.h[0])) * (lay0.bh[0] // max(1, lay0.v[0]))
             # no package of this file is larger (_PKG_FIXED): one pass; were it, the packer says so and gets its size
-            pkg = np.empty(_PKG_FIXED + _SEG_BYTES * (nmcu + 2) + nb, dtype=np.uint8)
-            rc = L.sp_jpeg_entropy_pack(ptr, nb, C.byref(lay), C.byref(scan), pkg.ctypes.data, pkg.size)
-            if rc == SP_JPEG_PKG_SMALL:
-                pkg = np.empty(scan.pkg_bytes, dtype=np.uint8)
-                rc = L.sp_jpeg_entropy_pack(ptr, nb, C.byref(lay), C.byref(scan), pkg.ctypes.data, pkg.size)
-            return rc, L.sp_last_error(), lay, scan, pkg
-
-        def need(lay, scan):
-            return (_a16(scan.pkg_bytes), _a16(scan.work_bytes), lay.total_blocks * 64, _a16(lay.plane_bytes),
-                    (3 * lay.width * lay.height + 255) & ~255)
+            first = np.empty(_PKG_FIXED + _SEG_BYTES * (nmcu + 2) + nb, dtype=np.uint8)
+            rc, lay, scan, pkg = _pack(L, ptr, nb, first, lambda lay, scan: np.empty(scan.pkg_bytes, dtype=np.uint8))
+            return rc, L.sp_last_error(), lay, scan, pkg  # (thread-local: read on the thread that made the call)
 
         st = self.batch_stats
         with self._lock:
@@ -467,17 +566,12 @@ class JpegDecoder:
                         elif rc == SP_JPEG_NOT_ELIGIBLE:
                             st["host"] += 1  # the host chunk decodes it
                         elif rc != SP_JPEG_UNSUPPORTED:  # (the host chunk refuses that one by the host rules)
-                            raise RuntimeError(f"sp_jpeg_entropy_pack: {msg.decode(errors='replace')}")
-                # the greedy chunk at the head of `pending`, by count and by the five buffer budgets
-                n, tot = 0, [0] * 5
-                for _, lay, scan, _ in pending:
-                    nd = need(lay, scan)
-                    if n and (n == SP_JPEG_BATCH_MAX or tot[0] + nd[0] + _ENT_TABLE_BYTES > KEEP_PKG
-                              or tot[1] + nd[1] > KEEP_PKG or tot[2] + nd[2] > KEEP_COEFS
-                              or tot[3] + nd[3] > KEEP_WORK or tot[4] + nd[4] > KEEP_ARENA):
-                        break
-                    n += 1
-                    tot = [a + b for a, b in zip(tot, nd)]
+                            raise _error(rc, "sp_jpeg_entropy_pack", msg)
+                # the greedy chunk at the head of `pending`: the packages plus both tables and the entropy workspaces
+                # within KEEP_PKG each, then the host chunks' three budgets
+                n = _greedy([(_a16(scan.pkg_bytes), _a16(scan.work_bytes)) + _chunk_need(lay)
+                             for _, lay, scan, _ in pending[:SP_JPEG_BATCH_MAX]],
+                            (KEEP_PKG - _ENT_TABLE_BYTES, KEEP_PKG, KEEP_COEFS, KEEP_WORK, KEEP_ARENA))
                 if n == 0 or (n == len(pending) and n < SP_JPEG_BATCH_MAX and pos < len(live)):
                     continue  # the chunk is still open and there are files left to pack
                 chunk, pending = pending[:n], pending[n:]
@@ -486,86 +580,43 @@ class JpegDecoder:
     def _gpu_entropy_chunk(self, L, chunk, lays, out):
         """One GPU-entropy chunk (lock held): plan both tables, run the device half, route the results."""
         n = len(chunk)
-        st = self.batch_stats
-        larr = (SpJpegLayout * n)(*[c[1] for c in chunk])
-        items, totals = (SpJpegBatchItem * n)(), SpJpegBatchTotals()
-        if L.sp_jpeg_batch_plan(larr, n, items, C.byref(totals)):
-            raise RuntimeError(f"sp_jpeg_batch_plan: {L.sp_last_error().decode(errors='replace')}")
+        larr, items, totals = _plan(L, [c[1] for c in chunk])
         ent, etot = (SpJpegEntropyItem * n)(), SpJpegEntropyTotals()
-        if L.sp_jpeg_entropy_batch_plan((SpJpegScan * n)(*[c[2] for c in chunk]), larr, items, n, ent, C.byref(etot)):
-            raise RuntimeError(f"sp_jpeg_entropy_batch_plan: {L.sp_last_error().decode(errors='replace')}")
+        _check(L.sp_jpeg_entropy_batch_plan((SpJpegScan * n)(*[c[2] for c in chunk]), larr, items, n, ent,
+                                            C.byref(etot)), "sp_jpeg_entropy_batch_plan")
         arena, flags, h2d = self._run_gpu_entropy_chunk(L, [c[3] for c in chunk], ent, etot, items, totals)
+        st = self.batch_stats
         st["chunks"] += 1
         st["h2d_bytes"] += h2d
         for k, (i, _, _, _) in enumerate(chunk):
             if flags[k]:  # the GPU result is discarded: the host chunk accepts the file or refuses it
                 st["fallback"][flags[k]] = st["fallback"].get(flags[k], 0) + 1
                 continue
-            it = items[k]
-            H, W = it.lay.height, it.lay.width
-            out[i] = arena[it.rgb_off:it.rgb_off + H * W * 3].view(H, W, 3)
+            out[i] = _view(arena, items[k])
             lays[i] = None
             st["gpu"] += 1
             st["images"] += 1
 
     def _run_gpu_entropy_chunk(self, L, pkgs, ent, etot, items, totals):
         """The device half of one GPU-entropy chunk (lock held): (RGB arena, status word per image, bytes uploaded).
-        Packages and both tables go into the pinned package buffer and up in one copy; decode()'s event discipline."""
-        n = len(pkgs)
+        Packages and both tables go into the pinned package buffer and up in one copy. (The host tests replace this
+        method with the CPU emulation of the launch chain: nothing above it touches the device.)"""
         ent_off = _a16(etot.pkg_bytes)
         tab_off = _a16(ent_off + C.sizeof(ent))
         nbytes = tab_off + C.sizeof(items)
-        need = {"pkg": (nbytes, KEEP_PKG, torch.uint8), "ent": (etot.work_bytes, KEEP_PKG, torch.uint8),
-                "coefs": (totals.coef_elems, KEEP_COEFS, torch.int16),
-                "work": (totals.work_bytes, KEEP_WORK, torch.uint8)}
-        kept = all(sz <= cap for sz, cap, _ in need.values())
-        g = self._g
-        if kept:
-            if self._copied is not None:
-                self._copied.synchronize()  # the pinned package buffer is free again
-            grow = any(g.get(k) is None or g[k].numel() < sz for k, (sz, _, _) in need.items())
-            grow = grow or g.get("pkg_host") is None or g["pkg_host"].numel() < nbytes
-            if grow and self._done is not None:
-                self._done.synchronize()  # the old buffers may still be read by the previous decode on another stream
-            _grow_kept(g, "pkg_host", nbytes, KEEP_PKG, dtype=torch.uint8, pin_memory=True)
-            for k, (sz, cap, dt) in need.items():
-                _grow_kept(g, k, sz, cap, dtype=dt, device=self.dev)
-            host, dev = g["pkg_host"], {k: g[k] for k in need}
-        else:
-            host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-            dev = {k: torch.empty(max(sz, 16), dtype=dt, device=self.dev) for k, (sz, _, dt) in need.items()}
-        hp = host.data_ptr()
+        b, kept = self._take({"pkg_host": (nbytes, KEEP_PKG, torch.uint8, None),
+                              "pkg": (nbytes, KEEP_PKG, torch.uint8, self.dev),
+                              "ent": (etot.work_bytes, KEEP_PKG, torch.uint8, self.dev),
+                              "coefs": (totals.coef_elems, KEEP_COEFS, torch.int16, self.dev),
+                              "work": (totals.work_bytes, KEEP_WORK, torch.uint8, self.dev)})
+        hp = b["pkg_host"].data_ptr()
         for k, pkg in enumerate(pkgs):
             C.memmove(hp + ent[k].pkg_off, pkg.ctypes.data, ent[k].scan.pkg_bytes)
         C.memmove(hp + ent_off, ent, C.sizeof(ent))
         C.memmove(hp + tab_off, items, C.sizeof(items))
-        cur = torch.cuda.current_stream(self.dev)
-        if kept and self._done is not None:
-            cur.wait_event(self._done)  # another stream's previous decode may still read the buffers
-        dev["pkg"][:nbytes].copy_(host[:nbytes], non_blocking=True)
-        copied = torch.cuda.Event()
-        copied.record()
-        arena = torch.empty(totals.rgb_bytes, dtype=torch.uint8, device=self.dev)
-        status = self._bstatus[:n]
-        status.zero_()
-        pp = dev["pkg"].data_ptr()
-        rc = L.sp_jpeg_entropy_batch_decode(pp, etot.pkg_bytes, pp + ent_off, ent, n, C.byref(etot),
-                                            dev["ent"].data_ptr(), dev["ent"].numel(), dev["coefs"].data_ptr(),
-                                            totals.coef_elems, status.data_ptr(), cur.cuda_stream)
-        if rc:
-            raise RuntimeError(f"sp_jpeg_entropy_batch_decode: {L.sp_last_error().decode(errors='replace')}")
-        rc = L.sp_jpeg_batch_to_rgb(dev["coefs"].data_ptr(), totals.coef_elems, pp + tab_off, items, n, C.byref(totals),
-                                    dev["work"].data_ptr(), dev["work"].numel(), arena.data_ptr(), arena.numel(),
-                                    status.data_ptr(), cur.cuda_stream)
-        if rc:
-            raise RuntimeError(f"sp_jpeg_batch_to_rgb: {L.sp_last_error().decode(errors='replace')}")
-        self._bstatus_host[:n].copy_(status, non_blocking=True)
-        done = torch.cuda.Event()
-        done.record(cur)
-        done.synchronize()
-        if kept:
-            self._copied, self._done = copied, done
-        return arena, self._bstatus_host[:n].tolist(), nbytes
+        arena, flags = self._batch_to_rgb(L, items, totals, kept, b["pkg_host"], b["pkg"], nbytes, tab_off, b["coefs"],
+                                          b["work"], entropy=(ent, etot, ent_off, b["ent"]))
+        return arena, flags, nbytes
 
     def _pool(self, workers):
         """The decoder's entropy-decode thread pool (created on first use, replaced when the size changes)."""
@@ -577,91 +628,11 @@ class JpegDecoder:
             self._workers = (workers, cf.ThreadPoolExecutor(max_workers=workers, thread_name_prefix="spotter-jpeg"))
         return self._workers[1]
 
-    def _decode_gpu_entropy(self, L, ptr, n, out):
-        """entropy="gpu": pack on the host into the reused pinned buffer, copy the package asynchronously, run the
-        entropy kernels and sp_jpeg_to_rgb, one status readback. The image, or None when the file takes the host path
-        (not eligible, or a non-zero status word); raises UnsupportedJpeg as the host parser does. Lock held."""
-        lay, scan = SpJpegLayout(), SpJpegScan()
-        g = self._g
-        if self._copied is not None:
-            self._copied.synchronize()  # the pinned package buffer is free again
-        host = g.get("pkg_host")
-        rc = L.sp_jpeg_entropy_pack(ptr, n, C.byref(lay), C.byref(scan), host.data_ptr() if host is not None else None,
-                                    host.numel() if host is not None else 0)
-        kept = True
-        if rc == SP_JPEG_PKG_SMALL:
-            _check_pixels(lay)
-            if scan.pkg_bytes > KEEP_PKG:
-                kept, host = False, torch.empty(scan.pkg_bytes, dtype=torch.uint8, pin_memory=True)
-            else:
-                _grow_kept(g, "pkg_host", scan.pkg_bytes, KEEP_PKG, dtype=torch.uint8, pin_memory=True)
-                host = g["pkg_host"]
-            rc = L.sp_jpeg_entropy_pack(ptr, n, C.byref(lay), C.byref(scan), host.data_ptr(), host.numel())
-        if rc == SP_JPEG_UNSUPPORTED:
-            raise UnsupportedJpeg(L.sp_last_error().decode(errors="replace"))
-        if rc == SP_JPEG_NOT_ELIGIBLE:
-            self.stats["host"] += 1
-            return None
-        if rc:
-            raise RuntimeError(f"sp_jpeg_entropy_pack: {L.sp_last_error().decode(errors='replace')}")
-        _check_pixels(lay)
-        ncoef = lay.total_blocks * 64
-        need = {"pkg": (scan.pkg_bytes, KEEP_PKG, torch.uint8), "ent": (scan.work_bytes, KEEP_PKG, torch.uint8),
-                "coefs": (ncoef, KEEP_COEFS, torch.int16), "work": (lay.plane_bytes, KEEP_WORK, torch.uint8)}
-        if any(sz > cap for sz, cap, _ in need.values()):
-            kept = False
-        if kept:
-            if any(g.get(k) is None or g[k].numel() < sz for k, (sz, _, _) in need.items()) and self._done is not None:
-                self._done.synchronize()  # the old buffers may still be read by the previous decode on another stream
-            for k, (sz, cap, dt) in need.items():
-                _grow_kept(g, k, sz, cap, dtype=dt, device=self.dev)
-            dev = {k: g[k] for k in need}
-        else:
-            dev = {k: torch.empty(max(sz, 16), dtype=dt, device=self.dev) for k, (sz, _, dt) in need.items()}
-        cur = torch.cuda.current_stream(self.dev)
-        if kept and self._done is not None:
-            cur.wait_event(self._done)  # another stream's previous decode may still read the buffers
-        dev["pkg"][:scan.pkg_bytes].copy_(host[:scan.pkg_bytes], non_blocking=True)
-        copied = torch.cuda.Event()
-        copied.record()
-        H, W = lay.height, lay.width
-        if out is None:
-            out = torch.empty((H, W, 3), dtype=torch.uint8, device=self.dev)
-        assert out.dtype == torch.uint8 and out.is_cuda and out.shape == (H, W, 3) and out.is_contiguous()
-        self._status.zero_()
-        rc = L.sp_jpeg_entropy_decode(dev["pkg"].data_ptr(), C.byref(scan), C.byref(lay), dev["ent"].data_ptr(),
-                                      dev["ent"].numel(), dev["coefs"].data_ptr(), dev["coefs"].numel(),
-                                      self._status.data_ptr(), cur.cuda_stream)
-        if rc:
-            raise RuntimeError(f"sp_jpeg_entropy_decode: {L.sp_last_error().decode(errors='replace')}")
-        rc = L.sp_jpeg_to_rgb(dev["coefs"].data_ptr(), C.byref(lay), dev["work"].data_ptr(), dev["work"].numel(),
-                              out.data_ptr(), W * 3, self._status.data_ptr(), cur.cuda_stream)
-        if rc:
-            raise RuntimeError(f"sp_jpeg_to_rgb: {L.sp_last_error().decode(errors='replace')}")
-        self._status_host.copy_(self._status, non_blocking=True)
-        done = torch.cuda.Event()
-        done.record(cur)
-        done.synchronize()
-        if kept:
-            self._copied, self._done = copied, done
-        self.stats["h2d_bytes"] += int(scan.pkg_bytes)
-        st = int(self._status_host[0])
-        if st:  # the GPU result is discarded; the host path accepts the file or raises UnsupportedJpeg by its own rules
-            self.stats["fallback"][st] = self.stats["fallback"].get(st, 0) + 1
-            return None
-        self.stats["gpu"] += 1
-        return out
+
 
 
 _decoders: dict = {}
 _dec_lock = threading.Lock()
-
-
-def _grow_kept(store: dict, key, n, cap, **kw):
-    """store[key] grown to hold n elements (at least 1 MiB worth, at most cap)."""
-    t = store.get(key)
-    if t is None or t.numel() < n:
-        store[key] = torch.empty(min(cap, max(n, 1 << 20)), **kw)
 
 
 class _ArrowArray(C.Structure):
@@ -721,15 +692,6 @@ class JpegEncoder:
             self._plans[key] = lay
         return lay
 
-    @staticmethod
-    def _grow(t, n, dtype, device=None, pinned=False):
-        if t is not None and t.numel() >= n:
-            return t
-        n = max(n, 1 << 20)
-        if pinned:
-            return torch.empty(n, dtype=dtype, pin_memory=True)
-        return torch.empty(n, dtype=dtype, device=device)
-
     def encode(self, src, quality=-1, subsampling=-1, comment: bytes | None = None) -> bytes:
         """src: a uint8 [H, W, 3] device tensor, or a PIL RGB image (its host pixels are uploaded)."""
         with self._lock:
@@ -744,15 +706,15 @@ class JpegEncoder:
                 W, H = src.size
                 hptr, stride, pb, keep_h = pil_pixels(src)
                 n = stride * H
-                self._stage = self._grow(self._stage, n, torch.uint8, pinned=True)
-                self._pix = self._grow(self._pix, n, torch.uint8, self.dev)
+                self._stage = _grow(self._stage, n, torch.uint8)
+                self._pix = _grow(self._pix, n, torch.uint8, self.dev)
                 C.memmove(self._stage.data_ptr(), hptr, n)
                 del keep_h
                 self._pix[:n].copy_(self._stage[:n], non_blocking=True)
                 ptr, keep = self._pix.data_ptr(), None
             lay = self.plan(W, H, quality, subsampling)
-            self._work = self._grow(self._work, lay.work_bytes, torch.uint8, self.dev)
-            self._bits = self._grow(self._bits, lay.bits_cap, torch.uint8, self.dev)
+            self._work = _grow(self._work, lay.work_bytes, torch.uint8, self.dev)
+            self._bits = _grow(self._bits, lay.bits_cap, torch.uint8, self.dev)
             rc = L.sp_jpeg_enc_rgb(ptr, stride, pb, C.byref(lay), self._work.data_ptr(), self._work.numel(),
                                    self._bits.data_ptr(), self._bits.numel(), self._nbits.data_ptr(), cur.cuda_stream)
             if rc:
@@ -763,7 +725,7 @@ class JpegEncoder:
             ev.synchronize()
             nbits = int(self._nbits_host[0])
             nbytes = (nbits + 7) // 8
-            self._down = self._grow(self._down, nbytes, torch.uint8, pinned=True)
+            self._down = _grow(self._down, nbytes, torch.uint8)
             self._down[:nbytes].copy_(self._bits[:nbytes], non_blocking=True)
             ev.record(cur)
             ev.synchronize()
@@ -925,8 +887,8 @@ class _DrawStage:
             if need > cap:
                 if self._done is not None:
                     self._done.synchronize()  # the old device table goes back to the caching allocator
-                self._stage = JpegEncoder._grow(None, need, torch.uint8, pinned=True)
-                self._table = JpegEncoder._grow(None, need, torch.uint8, self.dev)
+                self._stage = _grow(None, need, torch.uint8)
+                self._table = _grow(None, need, torch.uint8, self.dev)
                 need = lst.pack(self._stage.data_ptr(), self._stage.numel())
             if self._done is not None:
                 cur.wait_event(self._done)  # another stream's previous launch may still read the device table

@@ -263,6 +263,104 @@ def test_two_decoders_on_two_streams(dev, batch):
             _same(g, batch[i][2], batch[i][0])
 
 
+def _cap_needs(entropy, datas):
+    """What the decoder's run over `datas` (decode() of one file, or one decode_many chunk) asks of each KEEP_* cap,
+    and what decode_many's chunker counts against it for these files, from the library's own plans: the staging
+    layouts are spotter_amd/jpeg.py's (host entropy: the table behind the coefficients, 16-byte aligned; GPU entropy:
+    packages, entropy table, batch table, each 16-byte aligned, and the workspace against KEEP_PKG as well)."""
+    from spotter_amd import jpeg
+    from spotter_amd._lib import SpJpegEntropyItem, SpJpegEntropyTotals, SpJpegScan
+
+    def a16(v):
+        return (v + 15) & ~15
+
+    packed = [jpeg.pack_scan(d) for d in datas]
+    lays, scans, n = [p[0] for p in packed], [p[1] for p in packed], len(datas)
+    count = {"KEEP_COEFS": sum(lay.total_blocks * 64 for lay in lays),
+             "KEEP_WORK": sum(a16(lay.plane_bytes) for lay in lays)}
+    larr, items, tot = (SpJpegLayout * n)(*lays), (SpJpegBatchItem * n)(), SpJpegBatchTotals()
+    assert lib().sp_jpeg_batch_plan(larr, n, items, C.byref(tot)) == 0, lib().sp_last_error()
+    if entropy == "host":
+        chunk = {"KEEP_COEFS": ((tot.coef_elems + 7) & ~7) + (C.sizeof(items) + 1) // 2, "KEEP_WORK": tot.work_bytes}
+        one = {"KEEP_COEFS": lays[0].total_blocks * 64, "KEEP_WORK": lays[0].plane_bytes}
+        count["KEEP_COEFS"] += jpeg._TABLE_ELEMS
+    else:
+        ent, etot = (SpJpegEntropyItem * n)(), SpJpegEntropyTotals()
+        assert lib().sp_jpeg_entropy_batch_plan((SpJpegScan * n)(*scans), larr, items, n, ent, C.byref(etot)) == 0
+        nbytes = a16(a16(etot.pkg_bytes) + C.sizeof(ent)) + C.sizeof(items)
+        chunk = {"KEEP_PKG": max(nbytes, etot.work_bytes), "KEEP_COEFS": tot.coef_elems, "KEEP_WORK": tot.work_bytes}
+        one = {"KEEP_PKG": max(scans[0].pkg_bytes, scans[0].work_bytes), "KEEP_COEFS": lays[0].total_blocks * 64,
+               "KEEP_WORK": lays[0].plane_bytes}
+        count["KEEP_PKG"] = max(sum(a16(s.pkg_bytes) for s in scans) + jpeg._ENT_TABLE_BYTES,
+                                sum(a16(s.work_bytes) for s in scans))
+    return one, chunk, count
+
+
+@pytest.mark.parametrize("entropy", ["host", "gpu"])
+@pytest.mark.parametrize("form", ["decode", "decode_many"])
+def test_caps_exactly_met_keep_the_buffers_and_one_less_takes_temporaries(dev, monkeypatch, form, entropy):
+    """The KEEP_* caps at exactly what a call needs (the kept buffers serve it) and one less, each cap in turn (the
+    call, or in decode_many the larger file as a chunk of its own, runs through buffers of that call): the pixels
+    and the path counted are the normal decode's, the kept buffers are neither replaced nor added to, and the
+    decoder decodes normally afterwards."""
+    from spotter_amd import jpeg
+
+    by_name = dict(cases())
+    a, b = by_name["233x177 sub2"], by_name["17x33 sub1"]
+    d = jpeg.JpegDecoder(dev, entropy=entropy)
+    st = d.stats if form == "decode" else d.batch_stats
+    counted = ("gpu", "host") if form == "decode" else ("gpu", "host", "images", "refused", "flagged")
+    kept_flags, take = [], d._take
+
+    def spy(need):
+        got = take(need)
+        kept_flags.append(got[1])
+        return got
+
+    d._take = spy  # which of its store's two branches every run took
+
+    def run(files):
+        del kept_flags[:]
+        before = dict(st)
+        got = [d.decode(files[0])] if form == "decode" else d.decode_many(files, max_workers=1)
+        assert st["fallback"] == {} and all(torch.is_tensor(g) for g in got), (st, got)
+        return got, {k: st[k] - before[k] for k in counted}, st.get("chunks", 0) - before.get("chunks", 0)
+
+    def ptrs():
+        return {k: t.data_ptr() for k, t in d._kept.items()}
+
+    def same(got, want, what):
+        assert len(got[0]) == len(want[0]) and got[1] == want[1], (what, got[1], want[1])
+        for g, w in zip(got[0], want[0]):
+            assert g.shape == w.shape and torch.equal(g, w), what
+
+    for files in ([[a], [b]] if form == "decode" else [[a, b]]):
+        want = run(files)
+        assert all(kept_flags) and want[1]["gpu"] == (len(files) if entropy == "gpu" else 0), (kept_flags, want[1])
+        one, chunk, count = _cap_needs(entropy, files)
+        exact = one if form == "decode" else {k: max(chunk[k], count[k]) for k in chunk}
+        # (in decode_many one less than the call needs only splits the chunk: one less than the first file needs alone
+        # is what sends a run through temporaries)
+        less = one if form == "decode" else _cap_needs(entropy, files[:1])[1]
+        held = ptrs()
+        for name, v in exact.items():
+            monkeypatch.setattr(jpeg, name, v)
+        got = run(files)
+        same(got, want, ("exact", exact))
+        assert all(kept_flags) and got[2] == want[2] and ptrs() == held, (kept_flags, got[2], exact)
+        monkeypatch.undo()
+        for name, v in less.items():
+            monkeypatch.setattr(jpeg, name, v - 1)
+            got = run(files)
+            same(got, want, (name, v - 1))
+            assert not all(kept_flags) and ptrs() == held, (name, v - 1, kept_flags)
+            assert got[2] == (0 if form == "decode" else 2), (name, got[2])  # the larger file ran alone
+            monkeypatch.undo()
+            got = run(files)
+            same(got, want, ("after", name))
+            assert all(kept_flags) and got[2] == want[2] and ptrs() == held, (name, kept_flags)
+
+
 class _Recording:
     """A processor that keeps the pixel_values it produced."""
 

@@ -354,6 +354,32 @@ def test_decode_many_chunks_by_count_and_budget(packed, monkeypatch):
     assert [len(c) for c in d.gpu_chunks] == [1, 1, 1]
 
 
+def test_host_chunker_chunks_by_its_three_budgets(packed, monkeypatch):
+    """The host-entropy chunker's own budgets: KEEP_ARENA, KEEP_WORK, and KEEP_COEFS less the table that travels
+    behind the coefficients (jpeg._TABLE_ELEMS)."""
+    from spotter_amd import jpeg
+
+    good = dict(cases())
+    small, mid = good["2x3 sub0"], good["233x177 sub2"]
+    lay = packed["233x177 sub2"][0]
+    budgets = {"KEEP_ARENA": (3 * lay.width * lay.height + 255) & ~255, "KEEP_COEFS": lay.total_blocks * 64,
+               "KEEP_WORK": (lay.plane_bytes + 15) & ~15}
+    reserve = {"KEEP_ARENA": 0, "KEEP_COEFS": jpeg._TABLE_ELEMS, "KEEP_WORK": 0}
+    for name, per_image in budgets.items():
+        d = _stand_in(entropy="host")
+        monkeypatch.setattr(jpeg, name, 3 * per_image + reserve[name] + 1)  # three such files fit, a fourth does not
+        d.decode_many([mid] * 7 + [small], max_workers=1)
+        assert [len(c) for c in d.host_chunks] == [3, 3, 2], name
+        assert d.host_chunks == [[0, 1, 2], [3, 4, 5], [6, 7]] and not d.gpu_chunks, name
+        monkeypatch.undo()
+        # a file beyond the budget runs as a chunk of its own, between chunks of files that fit
+        d = _stand_in(entropy="host")
+        monkeypatch.setattr(jpeg, name, per_image + reserve[name] - 1)
+        d.decode_many([small, small, mid, small], max_workers=1)
+        assert d.host_chunks == [[0, 1], [2], [3]], name
+        monkeypatch.undo()
+
+
 def test_two_threads_with_different_pool_sizes_share_one_decoder(monkeypatch):
     """The pack phase uses the decoder's pool and counters under the decoder's lock: two callers that ask for
     different pool sizes (each replaces the executor) do not meet a shut-down pool or lose a count."""

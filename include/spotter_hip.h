@@ -668,6 +668,56 @@ int sp_jpeg_enc_finish(const sp_jpeg_enc_layout* lay, const uint8_t* bits, int64
                        int64_t comment_len, uint8_t* out, int64_t out_cap, int64_t* out_len);
 
 /*
+ * Batched encode (added under ABI v20): sp_jpeg_enc_rgb over up to SP_JPEG_BATCH_MAX images in six kernel launches
+ * whatever n is (FDCT, per-MCU bit counts, one scan workgroup per image, the segment offsets, the zeroing, the emit;
+ * no memset, no copy). The sources are separate device images; the images' workspaces share one buffer and their
+ * entropy-coded segments one packed bit buffer, whose layout the device works out from the bit counts. One table row
+ * per image says where its parts lie and which workgroups of the two launch shapes are its own (a workgroup never
+ * spans two images and finds its row by the uniform binary search sp_jpeg_batch_to_rgb uses). The kernels read the
+ * layout, quantiser tables included, from the row in device memory and run sp_jpeg_enc_rgb's own device code on it.
+ */
+#define SP_JPEG_ENC_FDCT_MCUS 4   /* MCUs per workgroup of the FDCT launch (one wave each, as sp_jpeg_enc_rgb) */
+#define SP_JPEG_ENC_WG_MCUS 256   /* MCUs per workgroup of the bit-count and emit launches (one thread each) */
+typedef struct {
+  sp_jpeg_enc_layout lay;  /* as sp_jpeg_enc_plan filled it */
+  const uint8_t* src;      /* the image's pixels: an absolute device pointer (the sources are separate tensors) */
+  int64_t row_stride;      /* bytes between its rows, >= pixel_bytes * width */
+  int64_t work_off;        /* byte offset of its workspace (lay.work_bytes, laid out as sp_jpeg_enc_rgb's) in the
+                              shared one, a multiple of 256 */
+  int32_t pixel_bytes;     /* 3 (RGB) or 4 (RGBX) */
+  int32_t first_wg_fdct;   /* its first workgroup in the FDCT launch: exclusive prefix sum of ceil(nmcu / 4) */
+  int32_t first_wg_mcu;    /* the same for the per-MCU launches: prefix sum of ceil(nmcu / 256) */
+  int32_t reserved;        /* 0 */
+} sp_jpeg_enc_batch_item;
+typedef struct {
+  int64_t work_bytes;      /* bytes of the shared workspace */
+  int64_t bits_cap;        /* bytes of the packed bit buffer: sum of the layouts' bits_cap, each rounded up to 16 */
+  int64_t wg_fdct;         /* workgroups of the FDCT launch */
+  int64_t wg_mcu;          /* workgroups of a per-MCU launch */
+} sp_jpeg_enc_batch_totals;
+/* Host: lay out n images: fills items[i] (a copy of lays[i], work_off, both prefix columns, reserved = 0; src,
+ * row_stride and pixel_bytes are the caller's to fill and are left alone) and *totals. Refused with -1 and a message:
+ * a NULL pointer, n outside [1, SP_JPEG_BATCH_MAX], a layout that is not sp_jpeg_enc_plan's, more than 2^31 - 1
+ * workgroups in a launch. No device call. */
+int sp_jpeg_enc_batch_plan(const sp_jpeg_enc_layout* lays, int n, sp_jpeg_enc_batch_item* items,
+                           sp_jpeg_enc_batch_totals* totals);
+/* Device: the six launches for the whole chunk. items_dev is the device copy of the table (8-byte aligned; it may
+ * travel in the same upload as host pixels), items_host the same bytes on the host, read here only to check the
+ * arguments before anything launches: every layout sp_jpeg_enc_plan's, every source non-null with pixel_bytes 3 or 4
+ * and row_stride >= pixel_bytes * width, every workspace range 256-byte aligned, inside work and the ranges pairwise
+ * disjoint, both prefix columns and *totals what the layouts give, work_bytes and bits_cap at least the totals', work
+ * 256-byte, bits 16-byte and result 8-byte aligned. A refused call returns -1 and launches nothing.
+ * Output: image i's segment, unstuffed and unpadded, MSB first, exactly the bytes sp_jpeg_enc_rgb writes, in
+ * bits[seg_off[i] : seg_off[i] + ceil(nbits[i] / 8)); seg_off is computed on the device, in input order, each a
+ * multiple of 16 (image i takes its zeroed words, 4 * (ceil(nbits[i] / 32) + 1) bytes, rounded up to 16; bytes
+ * between those words and the next segment are left alone). result: device int64 [2n + 1] = nbits[0..n),
+ * seg_off[0..n), the bytes used (the end of the last image's part): one small readback, then one download of
+ * exactly the used bytes. Asynchronous on `stream`; allocates nothing, makes no host-visible copy. */
+int sp_jpeg_enc_batch_rgb(const sp_jpeg_enc_batch_item* items_dev, const sp_jpeg_enc_batch_item* items_host, int n,
+                          const sp_jpeg_enc_batch_totals* totals, uint8_t* work, int64_t work_bytes, uint8_t* bits,
+                          int64_t bits_cap, int64_t* result, void* stream);
+
+/*
  * Label drawing (ABI v16): serve.py:119-137 `ImageDraw.Draw(image)`, `draw.rectangle`, `draw.text`, whose Python
  * half (colours, layout, anchors, stroke-then-fill) stays Pillow's and whose pixel half — ImagingDrawRectangle and
  * ImagingFill2 with an "L" mask — runs here on the device image (spotter_amd/draw.py records, this applies).

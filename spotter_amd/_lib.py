@@ -125,6 +125,18 @@ class SpJpegEncLayout(C.Structure):
     ]
 
 
+SP_JPEG_ENC_FDCT_MCUS, SP_JPEG_ENC_WG_MCUS = 4, 256
+
+
+class SpJpegEncBatchItem(C.Structure):
+    _fields_ = [("lay", SpJpegEncLayout), ("src", vp), ("row_stride", i64), ("work_off", i64), ("pixel_bytes", i32),
+                ("first_wg_fdct", i32), ("first_wg_mcu", i32), ("reserved", i32)]
+
+
+class SpJpegEncBatchTotals(C.Structure):
+    _fields_ = [("work_bytes", i64), ("bits_cap", i64), ("wg_fdct", i64), ("wg_mcu", i64)]
+
+
 class SpDrawOp(C.Structure):
     _fields_ = [
         ("kind", i32), ("x0", i32), ("y0", i32), ("x1", i32), ("y1", i32), ("ink", C.c_uint32),
@@ -234,6 +246,10 @@ _SIGS = {
     "sp_jpeg_enc_rgb": (i32, [vp, i64, i32, C.POINTER(SpJpegEncLayout), vp, i64, vp, i64, vp, vp]),
     "sp_jpeg_enc_max_bytes": (i64, [C.POINTER(SpJpegEncLayout), i64, i64]),
     "sp_jpeg_enc_finish": (i32, [C.POINTER(SpJpegEncLayout), vp, i64, vp, i64, vp, i64, C.POINTER(i64)]),
+    "sp_jpeg_enc_batch_plan": (i32, [C.POINTER(SpJpegEncLayout), i32, C.POINTER(SpJpegEncBatchItem),
+                                     C.POINTER(SpJpegEncBatchTotals)]),
+    "sp_jpeg_enc_batch_rgb": (i32, [vp, C.POINTER(SpJpegEncBatchItem), i32, C.POINTER(SpJpegEncBatchTotals), vp, i64,
+                                    vp, i64, vp, vp]),
     "sp_draw_pack": (i32, [vp, i32, vp, i64, i32, i32, vp, i64, C.POINTER(i64)]),
     "sp_draw_rgb": (i32, [vp, i32, i32, i64, vp, vp, i64, vp]),
     "sp_host_register": (i32, [vp, i64, C.POINTER(vp)]),

@@ -6,7 +6,7 @@ overlapped with the forward of the current one.
         ...  # {"size": (w, h), "scores", "labels", "boxes"} or {"error": str}, in input order
 
     python -m spotter_amd.bulk --model NAME [--precision P] [--batch 32] [--threshold 0.5]
-                               [--jpeg-entropy {host,gpu,auto}] --out results.jsonl PATH...
+                               [--jpeg-entropy {host,gpu,auto}] [--labelled-dir DIR] --out results.jsonl PATH...
 
 Per chunk of `batch` files, stage A (one host thread with a stream of its own) reads the files and decodes them with
 JpegDecoder.decode_many: one H2D copy, two launches and one status readback for the chunk. What decode_many returns
@@ -16,6 +16,10 @@ that file's {"error"} and the chunk runs without it. Stage B (the caller's threa
 runs processor → model → post_process_object_detection on the whole chunk. A of chunk i+1 runs while B of chunk i
 does, so two RGB arenas are alive at a time. One process, two threads and the decode pool; a failure of the GPU step
 propagates as the exception it is.
+
+With labelled=True every result also carries "jpeg", the labelled image /detect returns (serve.py:119-142): stage C,
+at the end of stage B, draws each chunk image's boxes and texts in place on the device and encodes the chunk with one
+JpegEncoder.encode_many.
 """
 from __future__ import annotations
 
@@ -35,6 +39,18 @@ def _read(item):
         return f.read()
 
 
+def _file_info(data: bytes) -> dict:
+    """What of the file's Pillow `info` its JPEG save writes back: the comment (JpegImagePlugin._save)."""
+    from PIL import Image
+
+    try:
+        with Image.open(io.BytesIO(data)) as im:
+            c = im.info.get("comment")
+    except Exception:  # noqa: BLE001 - a file Pillow refuses carries nothing
+        return {}
+    return {} if c is None else {"comment": c}
+
+
 def _pillow_rgb(data: bytes):
     """The reference's host decode (serve.py:96-97) as a uint8 [H, W, 3] array."""
     import numpy as np
@@ -49,21 +65,34 @@ class BulkDetector:
     SpotterImageProcessor, or anything with their call surface. decoder: the JpegDecoder to use (default: the
     device's shared decoder of entropy mode jpeg_entropy: "host", the default, or "gpu" / "auto", which decode the
     baseline files of a chunk in one GPU launch chain); decode_workers: decode_many's max_workers.
+    labelled: every successful result also carries "jpeg", the bytes /detect puts into labeled_image_base64 before
+    base64: for each detection whose label name (id2label[label], required) is a key of label_map, or for every
+    detection when label_map is None, a red rectangle of width 3 and the text (label_map's value, or the name) at
+    (x0 + 5, y0 + 5) in white with a black stroke of 1, then the image saved as JPEG at Pillow's defaults with the
+    source file's comment, as DeviceRGBImage.save writes it. A label_map key that is none of id2label's names is a
+    ValueError. encoder: the JpegEncoder to use (default: the device's shared one), or anything with encode_many.
     `stage_seconds` keeps the busy time of stage A and stage B of every chunk of the last detect() ("a" / "b",
-    seconds)."""
+    seconds), and with labelled=True that of the draw-plus-encode part ("c", not counted in "b")."""
 
     def __init__(self, model, processor, batch=32, threshold=0.5, decode_workers=None, decoder=None, device=None,
-                 jpeg_entropy="host"):
+                 jpeg_entropy="host", labelled=False, id2label=None, label_map=None, encoder=None):
         from .config import check_jpeg_entropy
 
         if int(batch) < 1:
             raise ValueError("batch must be at least 1")
+        if labelled and id2label is None:
+            raise ValueError("labelled=True needs id2label (the model's config.id2label)")
+        if label_map is not None and id2label is not None:
+            unknown = sorted(set(label_map) - set(id2label.values()))
+            if unknown:
+                raise ValueError(f"label_map names labels id2label does not have: {unknown}")
+        self.labelled, self.id2label, self.label_map, self._encoder = bool(labelled), id2label, label_map, encoder
         self.jpeg_entropy = check_jpeg_entropy(jpeg_entropy)
         self.model, self.processor = model, processor
         self.batch, self.threshold, self.decode_workers = int(batch), float(threshold), decode_workers
         self._decoder, self._device = decoder, device
         self._stream = None  # stage A's stream
-        self.stage_seconds = {"a": [], "b": []}
+        self.stage_seconds = {"a": [], "b": [], "c": []}
 
     # -- stage A: the decode thread ---------------------------------------------------------------------------
     def _gpu(self):
@@ -115,14 +144,16 @@ class BulkDetector:
                     images[k] = _pillow_rgb(d)
                 except Exception as e:  # noqa: BLE001 - whatever Pillow raises for a file it refuses
                     res[k] = {"error": f"{type(e).__name__}: {e}"}
+        infos = [_file_info(d) if im is not None else None for d, im in zip(datas, images)] if self.labelled else None
         self.stage_seconds["a"].append(time.perf_counter() - t0)
-        return res, images, event
+        return res, images, event, infos
 
     # -- stage B: the caller's thread and stream --------------------------------------------------------------
-    def _stage_b(self, res, images, event, gpu):
+    def _stage_b(self, res, images, event, gpu, infos=None):
         import torch
 
         t0 = time.perf_counter()
+        c = 0.0
         keep = [k for k, im in enumerate(images) if im is not None]
         if keep:
             batch = [images[k] for k in keep]
@@ -141,8 +172,72 @@ class BulkDetector:
                 outputs, threshold=self.threshold, target_sizes=[(h, w) for w, h in sizes])
             for k, size, d in zip(keep, sizes, dets):
                 res[k] = {"size": size, "scores": d["scores"], "labels": d["labels"], "boxes": d["boxes"]}
-        self.stage_seconds["b"].append(time.perf_counter() - t0)
+            if self.labelled:
+                t1 = time.perf_counter()
+                self._stage_c(res, keep, batch, infos, gpu)
+                c = time.perf_counter() - t1
+                self.stage_seconds["c"].append(c)
+        self.stage_seconds["b"].append(time.perf_counter() - t0 - c)
         return res
+
+    # -- stage C: draw and encode, at the end of stage B ------------------------------------------------------
+    def _stage_c(self, res, keep, batch, infos, gpu):
+        """serve.py:119-142 over the chunk: the draws through the drop-in's ImageDraw on a DeviceRGBImage over the
+        chunk's own pixels (in place: the forward has read them on this stream, and the arena is the chunk's), then
+        one encode_many. An image whose save the GPU encoder does not take (an unusual comment) is saved on its own,
+        by the rule DeviceRGBImage.save applies."""
+        from .draw import draw_module
+        from .jpeg import _gpu_jpeg_options
+
+        draw_mod = draw_module()
+        pictures = []
+        for k, im in zip(keep, batch):
+            picture = self._picture(im, infos[k], gpu)
+            draw = draw_mod.Draw(picture)
+            for lab, box in zip(res[k]["labels"].tolist(), res[k]["boxes"].tolist()):
+                text = self.id2label[int(lab)]
+                if self.label_map is not None:
+                    if text not in self.label_map:
+                        continue
+                    text = self.label_map[text]
+                draw.rectangle(box, outline="red", width=3)
+                draw.text(xy=(box[0] + 5, box[1] + 5), text=text, fill="white", stroke_width=1, stroke_fill="black")
+            pictures.append(picture)
+        opts = [_gpu_jpeg_options(p, io.BytesIO(), "JPEG", {}) for p in pictures]
+        together = [i for i, o in enumerate(opts) if o is not None]
+        enc = self._encoder
+        if enc is None:
+            from .jpeg import encoder
+
+            enc = self._encoder = encoder(gpu[0] if gpu is not None else None)
+        files = enc.encode_many([pictures[i] for i in together], comments=[opts[i][2] for i in together],
+                                max_workers=self.decode_workers)
+        for i, data in zip(together, files):
+            res[keep[i]]["jpeg"] = data
+        for i, o in enumerate(opts):
+            if o is None:
+                b = io.BytesIO()
+                pictures[i].save(b, format="JPEG")
+                res[keep[i]]["jpeg"] = b.getvalue()
+
+    def _picture(self, im, info, gpu):
+        """The chunk image as the PIL image the draws and the save work on: a DeviceRGBImage over the device pixels
+        (a host array from the Pillow fallback is uploaded), or, with a host stand-in for the decoder, Pillow's."""
+        import numpy as np
+
+        if gpu is None:
+            from PIL import Image
+
+            picture = Image.fromarray(np.ascontiguousarray(im))
+            picture.info.update(info)
+            return picture
+        import torch
+
+        from .jpeg import DeviceRGBImage
+
+        if not torch.is_tensor(im):
+            im = torch.tensor(np.asarray(im))  # a copy: Pillow's array is read-only
+        return DeviceRGBImage(im.to(gpu[0]), info=info)
 
     def detect(self, items):
         """items: an iterable of bytes or paths. Yields one result per item, in input order."""
@@ -156,7 +251,7 @@ class BulkDetector:
                     break
             return chunk
 
-        self.stage_seconds = {"a": [], "b": []}
+        self.stage_seconds = {"a": [], "b": [], "c": []}
         chunk = take()
         if not chunk:
             return
@@ -164,10 +259,10 @@ class BulkDetector:
         with cf.ThreadPoolExecutor(max_workers=1, thread_name_prefix="spotter-bulk") as ex:
             fut = ex.submit(self._stage_a, chunk, gpu)
             while fut is not None:
-                res, images, event = fut.result()
+                res, images, event, infos = fut.result()
                 chunk = take()
                 fut = ex.submit(self._stage_a, chunk, gpu) if chunk else None
-                yield from self._stage_b(res, images, event, gpu)
+                yield from self._stage_b(res, images, event, gpu, infos)
 
 
 def walk(paths):
@@ -188,8 +283,8 @@ def _detector(args):
 
     model = SpotterForObjectDetection.from_pretrained(args.model, precision=args.precision)
     proc = SpotterImageProcessor.from_pretrained(args.model)
-    return BulkDetector(model, proc, batch=args.batch, threshold=args.threshold,
-                        jpeg_entropy=args.jpeg_entropy), model.config.id2label
+    return BulkDetector(model, proc, batch=args.batch, threshold=args.threshold, jpeg_entropy=args.jpeg_entropy,
+                        labelled=args.labelled_dir is not None, id2label=model.config.id2label), model.config.id2label
 
 
 def main(argv=None, make_detector=_detector) -> int:
@@ -203,13 +298,22 @@ def main(argv=None, make_detector=_detector) -> int:
     ap.add_argument("--threshold", type=float, default=0.5)
     ap.add_argument("--jpeg-entropy", choices=JPEG_ENTROPY_MODES, default=jpeg_entropy_from_env(),
                     help="where baseline JPEGs are Huffman-decoded (default: SPOTTER_JPEG_ENTROPY, i.e. host)")
+    ap.add_argument("--labelled-dir", metavar="DIR", default=None,
+                    help="also write every file's labelled image (boxes and label names drawn, as /detect returns it) "
+                         "to DIR/<index:06d>_<basename>.jpg")
     ap.add_argument("--out", required=True, help="JSON lines, one per file")
     ap.add_argument("paths", nargs="+", metavar="PATH", help="files, or directories walked in sorted order")
     args = ap.parse_args(argv)
     files = walk(args.paths)
     det, id2label = make_detector(args)
+    if args.labelled_dir is not None:
+        os.makedirs(args.labelled_dir, exist_ok=True)
     with open(args.out, "w") as out:
-        for path, r in zip(files, det.detect(files)):
+        for index, (path, r) in enumerate(zip(files, det.detect(files))):
+            if args.labelled_dir is not None and "jpeg" in r:
+                name = f"{index:06d}_{os.path.splitext(os.path.basename(path))[0]}.jpg"
+                with open(os.path.join(args.labelled_dir, name), "wb") as f:
+                    f.write(r["jpeg"])
             if "error" in r:
                 line = {"file": path, "error": r["error"]}
             else:

@@ -64,6 +64,19 @@ __device__ __forceinline__ int xcd_index(int b, int nwg) {
   return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
 }
 
+// The row of a batch table (jpeg.hip's decode, jpeg_enc.hip's encode) that owns workgroup `wg` of a launch: the last
+// row whose first-workgroup entry (an exclusive prefix sum, strictly increasing: every image has at least one
+// workgroup) is <= wg. Every lane of the workgroup takes the same path.
+template <typename Item>
+__device__ __forceinline__ int batch_image(const Item* __restrict__ items, int n, int32_t Item::*first, int wg) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (items[mid].*first <= wg) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // Register vectors of the MFMA kernels: operand fragments and accumulators.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

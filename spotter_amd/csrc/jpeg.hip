@@ -220,16 +220,7 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const sp_jpeg_layout L,
 // ------------------------------------------------------------------------------------------------ batched
 // The same two passes over a batch of images in one launch each: a workgroup serves one image, found by a uniform
 // binary search of the items' first-workgroup column (an exclusive prefix sum, strictly increasing: every image
-// has at least one block and one pixel), as sp_copy_segments finds its segment.
-__device__ __forceinline__ int batch_image(const sp_jpeg_batch_item* __restrict__ items, int n,
-                                           int32_t sp_jpeg_batch_item::*first, int wg) {
-  int lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (items[mid].*first <= wg) lo = mid; else hi = mid;
-  }
-  return lo;
-}
+// has at least one block and one pixel), as sp_copy_segments finds its segment: batch_image (common.h).
 
 __global__ __launch_bounds__(256) void jpeg_idct_batch_kernel(const int16_t* __restrict__ coefs, int64_t coef_elems,
                                                               const sp_jpeg_batch_item* __restrict__ items, int n,

@@ -20,6 +20,12 @@
 // tests/test_gpu_jpeg_enc_stages.py reads every stage's output off the workspace (coefficients, per-MCU bit
 // counts, offsets and total, the raw code stream) and compares it exactly with the oracle's, on inputs chosen for
 // the block, MCU-count and entropy-walk edges (tests/jpeg_enc_cases.py).
+//
+// sp_jpeg_enc_batch_rgb runs the same passes over up to SP_JPEG_BATCH_MAX images in six launches whatever their
+// number: the bodies of the four kernels are __device__ functions that the single-image kernels call
+// on their kernel-argument layout and the batched ones on the image's row of a table in device memory. Between
+// scan (one workgroup per image) and emit, jpeg_seg_batch_kernel turns the n bit counts into the 16-byte aligned
+// segment offsets of one packed bit buffer and jpeg_zero_batch_kernel zeroes the segments' words.
 #include "common.h"
 #include "jpeg_host.h"
 
@@ -80,14 +86,16 @@ __device__ __forceinline__ void fdct_1d(const int (&d)[8], int (&o)[8]) {
 
 constexpr int kMcuPerWg = 4;  // one wave per MCU
 
-__global__ __launch_bounds__(256) void jpeg_fdct_kernel(const uint8_t* __restrict__ rgb, int64_t stride, int pb,
-                                                        const sp_jpeg_enc_layout L, int16_t* __restrict__ coefs) {
+// Workgroup `wg` of an image's FDCT pass (4 MCUs, one wave each). Every thread reaches both barriers whatever MCU
+// it serves: waves past the image's last MCU only skip the work between them.
+__device__ __forceinline__ void fdct_workgroup(const uint8_t* __restrict__ rgb, int64_t stride, int pb,
+                                               const sp_jpeg_enc_layout& L, int16_t* __restrict__ coefs, int64_t wg) {
   __shared__ int ws[kMcuPerWg][6][8][9];
   __shared__ int qv[kMcuPerWg][6][64];
   __shared__ uint8_t nat_of_zz[64];
   if (threadIdx.x < 64) nat_of_zz[kZigzag[threadIdx.x]] = (uint8_t)threadIdx.x;  // read after the barriers below
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t mcu = (int64_t)blockIdx.x * kMcuPerWg + w;
+  const int64_t mcu = wg * kMcuPerWg + w;
   const int64_t nmcu = (int64_t)L.mcux * L.mcuy;
   const int j = lane >> 3, r = lane & 7;  // block within the MCU, row (pass 1) / column (pass 2)
   const int ny = L.h0 * L.v0;
@@ -194,6 +202,11 @@ __global__ __launch_bounds__(256) void jpeg_fdct_kernel(const uint8_t* __restric
   *reinterpret_cast<int4*>(dst + 8 * r) = pk;
 }
 
+__global__ __launch_bounds__(256) void jpeg_fdct_kernel(const uint8_t* __restrict__ rgb, int64_t stride, int pb,
+                                                        const sp_jpeg_enc_layout L, int16_t* __restrict__ coefs) {
+  fdct_workgroup(rgb, stride, pb, L, coefs, (int64_t)blockIdx.x);
+}
+
 __device__ __forceinline__ int nbits_of(int a) { return a ? 32 - __clz(a) : 0; }
 
 // Walks one MCU's blocks in scan order and hands every (code, length) / (magnitude bits, count) to `put`:
@@ -252,20 +265,24 @@ __device__ __forceinline__ void walk_mcu(const int16_t* __restrict__ coefs, cons
   }
 }
 
+// the Huffman-coded length of one MCU
+__device__ __forceinline__ int mcu_bits(const int16_t* __restrict__ coefs, const sp_jpeg_enc_layout& L, int64_t mcu) {
+  int n = 0;
+  walk_mcu(coefs, L, mcu, [&](uint32_t, int len) { n += len; });
+  return n;
+}
+
 __global__ __launch_bounds__(256) void jpeg_mcu_bits_kernel(const int16_t* __restrict__ coefs,
                                                             const sp_jpeg_enc_layout L, int32_t* __restrict__ bits) {
   const int64_t mcu = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (mcu >= (int64_t)L.mcux * L.mcuy) return;
-  int n = 0;
-  walk_mcu(coefs, L, mcu, [&](uint32_t, int len) { n += len; });
-  bits[mcu] = n;
+  bits[mcu] = mcu_bits(coefs, L, mcu);
 }
 
-// exclusive prefix sum of the per-MCU bit counts (one workgroup, each thread a contiguous chunk), the total at
-// total[0], then the words [0, ceil(total / 32)] of the bit buffer zeroed for the atomic ORs of the emit pass
-__global__ __launch_bounds__(1024) void jpeg_scan_kernel(const int32_t* __restrict__ bits, int64_t n,
-                                                         int64_t* __restrict__ off, int64_t* __restrict__ total,
-                                                         uint32_t* __restrict__ words, int64_t words_cap) {
+// One workgroup of 1024 threads: exclusive prefix sum of the per-MCU bit counts (each thread a contiguous chunk)
+// into off, the total at total[0] and returned to every thread.
+__device__ __forceinline__ int64_t scan_workgroup(const int32_t* __restrict__ bits, int64_t n,
+                                                  int64_t* __restrict__ off, int64_t* __restrict__ total) {
   __shared__ int64_t part[1024];
   const int t = threadIdx.x;
   const int64_t chunk = (n + 1023) / 1024;
@@ -287,15 +304,25 @@ __global__ __launch_bounds__(1024) void jpeg_scan_kernel(const int32_t* __restri
   }
   const int64_t tot = part[1023];
   if (t == 0) total[0] = tot;
-  const int64_t nw = (tot + 31) / 32 + 1;
+  return tot;
+}
+
+// the words a segment of `nbits` bits has zeroed for the atomic ORs of the emit pass: [0, ceil(nbits / 32)]
+__device__ __forceinline__ int64_t zeroed_words(int64_t nbits) { return (nbits + 31) / 32 + 1; }
+
+// the scan, then the words of the bit buffer zeroed
+__global__ __launch_bounds__(1024) void jpeg_scan_kernel(const int32_t* __restrict__ bits, int64_t n,
+                                                         int64_t* __restrict__ off, int64_t* __restrict__ total,
+                                                         uint32_t* __restrict__ words, int64_t words_cap) {
+  const int64_t nw = zeroed_words(scan_workgroup(bits, n, off, total));
+  const int t = threadIdx.x;
   for (int64_t i = t; i < nw; i += 1024) SP_BCHECK(i, words_cap);
   for (int64_t i = t; i < nw; i += 1024) words[i] = 0;
 }
 
-__global__ __launch_bounds__(256) void jpeg_emit_kernel(const int16_t* __restrict__ coefs, const sp_jpeg_enc_layout L,
-                                                        const int64_t* __restrict__ off, uint32_t* __restrict__ words) {
-  const int64_t mcu = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (mcu >= (int64_t)L.mcux * L.mcuy) return;
+// One MCU's codes written at its offset. words_cap: the 32-bit words of the image's own bit buffer bound.
+__device__ __forceinline__ void emit_mcu(const int16_t* __restrict__ coefs, const sp_jpeg_enc_layout& L,
+                                         const int64_t* __restrict__ off, uint32_t* __restrict__ words, int64_t mcu) {
   const int64_t o = off[mcu];
   int64_t wi = o >> 5;
   uint64_t acc = 0;  // pending bits, left-aligned; the first (o & 31) belong to the previous MCU's word
@@ -313,6 +340,123 @@ __global__ __launch_bounds__(256) void jpeg_emit_kernel(const int16_t* __restric
   });
   if (nacc > 0) SP_BCHECK(wi, L.bits_cap / 4);
   if (nacc > 0) atomicOr(words + wi, __builtin_bswap32((uint32_t)(acc >> 32)));
+}
+
+__global__ __launch_bounds__(256) void jpeg_emit_kernel(const int16_t* __restrict__ coefs, const sp_jpeg_enc_layout L,
+                                                        const int64_t* __restrict__ off, uint32_t* __restrict__ words) {
+  const int64_t mcu = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (mcu >= (int64_t)L.mcux * L.mcuy) return;
+  emit_mcu(coefs, L, off, words, mcu);
+}
+
+// ------------------------------------------------------------------------------------------------ batched
+// The same passes over a batch of images, one launch each: a workgroup serves one image, found by the uniform binary
+// search of the table's first-workgroup column (batch_image, common.h), and runs the device functions above on the
+// layout in that row. An image's workspace is the single-image one at its work_off.
+struct EncWork {
+  int64_t* total;
+  int64_t* off;
+  int32_t* mbits;
+  int16_t* coefs;
+};
+__device__ __forceinline__ EncWork enc_work(uint8_t* __restrict__ work, const sp_jpeg_enc_batch_item& it) {
+  const int64_t nmcu = (int64_t)it.lay.mcux * it.lay.mcuy;
+  EncWork w;
+  w.total = reinterpret_cast<int64_t*>(work + it.work_off);
+  w.off = w.total + 1;
+  w.mbits = reinterpret_cast<int32_t*>(w.off + nmcu);
+  w.coefs = reinterpret_cast<int16_t*>(work + it.work_off + (8 + 12 * nmcu + 255) / 256 * 256);  // enc_coef_offset
+  return w;
+}
+
+__global__ __launch_bounds__(256) void jpeg_fdct_batch_kernel(const sp_jpeg_enc_batch_item* __restrict__ items, int n,
+                                                              uint8_t* __restrict__ work, int64_t work_bytes) {
+  const int img = batch_image(items, n, &sp_jpeg_enc_batch_item::first_wg_fdct, (int)blockIdx.x);
+  SP_BCHECK(img, n);
+  const sp_jpeg_enc_batch_item& it = items[img];
+  const int64_t wg = (int64_t)blockIdx.x - it.first_wg_fdct;
+  SP_BCHECK(wg, ((int64_t)it.lay.mcux * it.lay.mcuy + kMcuPerWg - 1) / kMcuPerWg);
+  SP_BCHECK(it.work_off + it.lay.work_bytes - 1, work_bytes);
+  fdct_workgroup(it.src, it.row_stride, it.pixel_bytes, it.lay, enc_work(work, it).coefs, wg);
+}
+
+__global__ __launch_bounds__(256) void jpeg_mcu_bits_batch_kernel(const sp_jpeg_enc_batch_item* __restrict__ items,
+                                                                  int n, uint8_t* __restrict__ work,
+                                                                  int64_t work_bytes) {
+  const int img = batch_image(items, n, &sp_jpeg_enc_batch_item::first_wg_mcu, (int)blockIdx.x);
+  SP_BCHECK(img, n);
+  const sp_jpeg_enc_batch_item& it = items[img];
+  const int64_t mcu = ((int64_t)blockIdx.x - it.first_wg_mcu) * 256 + threadIdx.x;
+  if (mcu >= (int64_t)it.lay.mcux * it.lay.mcuy) return;
+  SP_BCHECK(it.work_off + it.lay.work_bytes - 1, work_bytes);
+  const EncWork w = enc_work(work, it);
+  w.mbits[mcu] = mcu_bits(w.coefs, it.lay, mcu);
+}
+
+// one workgroup per image; result[img] = the image's bit count
+__global__ __launch_bounds__(1024) void jpeg_scan_batch_kernel(const sp_jpeg_enc_batch_item* __restrict__ items, int n,
+                                                               uint8_t* __restrict__ work,
+                                                               int64_t* __restrict__ result) {
+  const int img = (int)blockIdx.x;
+  SP_BCHECK(img, n);
+  const sp_jpeg_enc_batch_item& it = items[img];
+  const EncWork w = enc_work(work, it);
+  const int64_t tot = scan_workgroup(w.mbits, (int64_t)it.lay.mcux * it.lay.mcuy, w.off, w.total);
+  if (threadIdx.x == 0) result[img] = tot;
+}
+
+// the bytes image i takes in the packed buffer: its zeroed words, rounded up to 16
+__device__ __forceinline__ int64_t seg_bytes(int64_t nbits) { return (zeroed_words(nbits) * 4 + 15) & ~(int64_t)15; }
+
+// one workgroup of SP_JPEG_BATCH_MAX threads: result[n + i] = seg_off[i], the exclusive prefix sum of the images'
+// parts in input order; result[2n] = the bytes used
+__global__ __launch_bounds__(SP_JPEG_BATCH_MAX) void jpeg_seg_batch_kernel(int n, int64_t* __restrict__ result) {
+  __shared__ int64_t sz[SP_JPEG_BATCH_MAX];
+  const int t = threadIdx.x;
+  sz[t] = t < n ? seg_bytes(result[t]) : 0;
+  __syncthreads();
+  int64_t o = 0;
+  for (int k = 0; k < t; ++k) o += sz[k];
+  if (t < n) result[n + t] = o;
+  if (t == n - 1) result[2 * n] = o + sz[t];
+}
+
+// Zeroes every segment's words: 16 bytes per thread, 4096 per workgroup, over a grid sized by the buffer's capacity;
+// workgroups past the bytes the device found in use return at once. A thread's 16 bytes lie inside one image's part
+// (parts start at multiples of 16); the words of the part past the image's zeroed ones are left alone.
+__global__ __launch_bounds__(256) void jpeg_zero_batch_kernel(int n, const int64_t* __restrict__ result,
+                                                              uint8_t* __restrict__ bits, int64_t bits_cap) {
+  const int64_t used = result[2 * n];
+  if ((int64_t)blockIdx.x * 4096 >= used) return;
+  const int64_t b = (int64_t)blockIdx.x * 4096 + threadIdx.x * 16;
+  if (b >= used) return;
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (result[n + mid] <= b) lo = mid; else hi = mid;
+  }
+  const int64_t end = result[n + lo] + zeroed_words(result[lo]) * 4;
+  SP_BCHECK(b + 15, bits_cap);
+  if (b + 16 <= end) {
+    *reinterpret_cast<uint4*>(bits + b) = make_uint4(0u, 0u, 0u, 0u);
+  } else {
+    for (int64_t p = b; p < end; p += 4) *reinterpret_cast<uint32_t*>(bits + p) = 0u;
+  }
+}
+
+__global__ __launch_bounds__(256) void jpeg_emit_batch_kernel(const sp_jpeg_enc_batch_item* __restrict__ items, int n,
+                                                              uint8_t* __restrict__ work,
+                                                              const int64_t* __restrict__ result,
+                                                              uint8_t* __restrict__ bits, int64_t bits_cap) {
+  const int img = batch_image(items, n, &sp_jpeg_enc_batch_item::first_wg_mcu, (int)blockIdx.x);
+  SP_BCHECK(img, n);
+  const sp_jpeg_enc_batch_item& it = items[img];
+  const int64_t mcu = ((int64_t)blockIdx.x - it.first_wg_mcu) * 256 + threadIdx.x;
+  if (mcu >= (int64_t)it.lay.mcux * it.lay.mcuy) return;
+  const EncWork w = enc_work(work, it);
+  const int64_t seg = result[n + img];
+  SP_BCHECK(seg + seg_bytes(result[img]) - 1, bits_cap);
+  emit_mcu(w.coefs, it.lay, w.off, reinterpret_cast<uint32_t*>(bits + seg), mcu);
 }
 
 }  // namespace
@@ -364,6 +508,43 @@ extern "C" int sp_jpeg_enc_rgb(const uint8_t* rgb, int64_t row_stride, int32_t p
     return -1;
   }
   return 0;
+}
+
+extern "C" int sp_jpeg_enc_batch_plan(const sp_jpeg_enc_layout* lays, int n, sp_jpeg_enc_batch_item* items,
+                                      sp_jpeg_enc_batch_totals* totals) {
+  return sp::jpeg_host::enc_batch_plan(lays, n, items, totals);
+}
+
+extern "C" int sp_jpeg_enc_batch_rgb(const sp_jpeg_enc_batch_item* items_dev, const sp_jpeg_enc_batch_item* items_host,
+                                     int n, const sp_jpeg_enc_batch_totals* totals, uint8_t* work, int64_t work_bytes,
+                                     uint8_t* bits, int64_t bits_cap, int64_t* result, void* stream) {
+  using namespace sp;
+  SP_ARG_CHECK(items_dev && items_host && totals && work && bits && result, "sp_jpeg_enc_batch_rgb: null args");
+  SP_ARG_CHECK((reinterpret_cast<uintptr_t>(items_dev) & 7) == 0 && (reinterpret_cast<uintptr_t>(work) & 255) == 0 &&
+                   (reinterpret_cast<uintptr_t>(bits) & 15) == 0 && (reinterpret_cast<uintptr_t>(result) & 7) == 0,
+               "sp_jpeg_enc_batch_rgb: misaligned buffer (table 8, work 256, bits 16, result 8 bytes)");
+  if (int rc = jpeg_host::enc_batch_check(items_host, n, totals, work_bytes, bits_cap)) return rc;
+  // the zeroing launch covers the capacity the totals give (what the segments can take), 4096 bytes a workgroup
+  const int64_t wg_zero = (totals->bits_cap + 4095) / 4096;
+  SP_ARG_CHECK(wg_zero <= INT32_MAX, "sp_jpeg_enc_batch_rgb: too many workgroups");
+  hipStream_t s = as_stream(stream);
+  const unsigned gm = (unsigned)totals->wg_mcu;
+  hipLaunchKernelGGL(jpeg_fdct_batch_kernel, dim3((unsigned)totals->wg_fdct), dim3(256), 0, s, items_dev, n, work,
+                     work_bytes);
+  int rc = check_launch("sp_jpeg_enc_batch_rgb(fdct)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(jpeg_mcu_bits_batch_kernel, dim3(gm), dim3(256), 0, s, items_dev, n, work, work_bytes);
+  if ((rc = check_launch("sp_jpeg_enc_batch_rgb(bits)"))) return rc;
+  hipLaunchKernelGGL(jpeg_scan_batch_kernel, dim3((unsigned)n), dim3(1024), 0, s, items_dev, n, work, result);
+  if ((rc = check_launch("sp_jpeg_enc_batch_rgb(scan)"))) return rc;
+  hipLaunchKernelGGL(jpeg_seg_batch_kernel, dim3(1), dim3(SP_JPEG_BATCH_MAX), 0, s, n, result);
+  if ((rc = check_launch("sp_jpeg_enc_batch_rgb(seg)"))) return rc;
+  hipLaunchKernelGGL(jpeg_zero_batch_kernel, dim3((unsigned)wg_zero), dim3(256), 0, s, n, result, bits,
+                     totals->bits_cap);
+  if ((rc = check_launch("sp_jpeg_enc_batch_rgb(zero)"))) return rc;
+  hipLaunchKernelGGL(jpeg_emit_batch_kernel, dim3(gm), dim3(256), 0, s, items_dev, n, work, result, bits,
+                     totals->bits_cap);
+  return check_launch("sp_jpeg_enc_batch_rgb(emit)");
 }
 
 extern "C" int64_t sp_jpeg_enc_max_bytes(const sp_jpeg_enc_layout* lay, int64_t nbits, int64_t comment_len) {

@@ -1088,5 +1088,91 @@ inline int batch_plan(const sp_jpeg_layout* lays, int n, sp_jpeg_batch_item* ite
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------ encode batch plan
+// Host half of the batched encode (sp_jpeg_enc_batch_plan, and the check sp_jpeg_enc_batch_rgb runs on the host copy
+// of its table before it launches anything).
+inline int64_t enc_fdct_wgs(const sp_jpeg_enc_layout& L) {
+  return ((int64_t)L.mcux * L.mcuy + SP_JPEG_ENC_FDCT_MCUS - 1) / SP_JPEG_ENC_FDCT_MCUS;
+}
+inline int64_t enc_mcu_wgs(const sp_jpeg_enc_layout& L) {
+  return ((int64_t)L.mcux * L.mcuy + SP_JPEG_ENC_WG_MCUS - 1) / SP_JPEG_ENC_WG_MCUS;
+}
+
+// sp_jpeg_enc_rgb's layout rule: the layout is byte for byte what enc_plan gives for its own parameters.
+inline int check_enc_layout(const sp_jpeg_enc_layout* lay, const char* who, int i) {
+  sp_jpeg_enc_layout chk;
+  const int sub = lay->h0 == 1 ? 0 : (lay->v0 == 1 ? 1 : 2);
+  SP_JPEG_REQUIRE(enc_plan(lay->width, lay->height, lay->quality, sub, &chk) == 0 && memcmp(&chk, lay, sizeof(chk)) == 0,
+                  "%s: image %d: layout is not sp_jpeg_enc_plan's", who, i);
+  return 0;
+}
+
+inline int enc_batch_plan(const sp_jpeg_enc_layout* lays, int n, sp_jpeg_enc_batch_item* items,
+                          sp_jpeg_enc_batch_totals* totals) {
+  SP_JPEG_REQUIRE(lays && items && totals, "sp_jpeg_enc_batch_plan: null args");
+  SP_JPEG_REQUIRE(n >= 1 && n <= SP_JPEG_BATCH_MAX, "sp_jpeg_enc_batch_plan: n = %d outside [1, %d]", n,
+                  SP_JPEG_BATCH_MAX);
+  sp_jpeg_enc_batch_totals t = {0, 0, 0, 0};
+  for (int i = 0; i < n; ++i) {
+    if (int rc = check_enc_layout(&lays[i], "sp_jpeg_enc_batch_plan", i)) return rc;
+    sp_jpeg_enc_batch_item& it = items[i];
+    it.lay = lays[i];
+    it.work_off = t.work_bytes;
+    it.first_wg_fdct = (int32_t)t.wg_fdct;
+    it.first_wg_mcu = (int32_t)t.wg_mcu;
+    it.reserved = 0;
+    t.work_bytes += (lays[i].work_bytes + 255) & ~255LL;
+    t.bits_cap += (lays[i].bits_cap + 15) & ~15LL;
+    t.wg_fdct += enc_fdct_wgs(lays[i]);
+    t.wg_mcu += enc_mcu_wgs(lays[i]);
+    SP_JPEG_REQUIRE(t.wg_fdct <= INT32_MAX && t.wg_mcu <= INT32_MAX,
+                    "sp_jpeg_enc_batch_plan: more than 2^31 - 1 workgroups at image %d", i);
+  }
+  *totals = t;
+  return 0;
+}
+
+inline int enc_batch_check(const sp_jpeg_enc_batch_item* items, int n, const sp_jpeg_enc_batch_totals* totals,
+                           int64_t work_bytes, int64_t bits_cap) {
+  const char* who = "sp_jpeg_enc_batch_rgb";
+  SP_JPEG_REQUIRE(items && totals, "%s: null args", who);
+  SP_JPEG_REQUIRE(n >= 1 && n <= SP_JPEG_BATCH_MAX, "%s: n = %d outside [1, %d]", who, n, SP_JPEG_BATCH_MAX);
+  int64_t wg_fdct = 0, wg_mcu = 0, cap = 0;
+  for (int i = 0; i < n; ++i) {
+    const sp_jpeg_enc_batch_item& it = items[i];
+    const sp_jpeg_enc_layout& L = it.lay;
+    if (int rc = check_enc_layout(&L, who, i)) return rc;
+    SP_JPEG_REQUIRE(it.src, "%s: image %d: null source", who, i);
+    SP_JPEG_REQUIRE(it.pixel_bytes == 3 || it.pixel_bytes == 4, "%s: image %d: pixel_bytes %d", who, i,
+                    it.pixel_bytes);
+    SP_JPEG_REQUIRE(it.row_stride >= (int64_t)it.pixel_bytes * L.width && it.row_stride <= (1LL << 40),
+                    "%s: image %d: row_stride %lld outside [%lld, 2^40]", who, i, (long long)it.row_stride,
+                    (long long)it.pixel_bytes * L.width);
+    SP_JPEG_REQUIRE(it.work_off >= 0 && (it.work_off & 255) == 0 && it.work_off <= work_bytes &&
+                        L.work_bytes <= work_bytes - it.work_off,
+                    "%s: image %d: workspace [%lld, +%lld) misaligned or outside work's %lld bytes", who, i,
+                    (long long)it.work_off, (long long)L.work_bytes, (long long)work_bytes);
+    SP_JPEG_REQUIRE(it.first_wg_fdct == wg_fdct && it.first_wg_mcu == wg_mcu,
+                    "%s: image %d: first workgroups %d / %d, its predecessors give %lld / %lld", who, i,
+                    it.first_wg_fdct, it.first_wg_mcu, (long long)wg_fdct, (long long)wg_mcu);
+    wg_fdct += enc_fdct_wgs(L);
+    wg_mcu += enc_mcu_wgs(L);
+    cap += (L.bits_cap + 15) & ~15LL;
+    SP_JPEG_REQUIRE(wg_fdct <= INT32_MAX && wg_mcu <= INT32_MAX, "%s: too many workgroups", who);
+    for (int k = 0; k < i; ++k)
+      SP_JPEG_REQUIRE(it.work_off + L.work_bytes <= items[k].work_off ||
+                          items[k].work_off + items[k].lay.work_bytes <= it.work_off,
+                      "%s: workspaces of images %d and %d overlap", who, k, i);
+  }
+  SP_JPEG_REQUIRE(totals->wg_fdct == wg_fdct && totals->wg_mcu == wg_mcu && totals->bits_cap == cap,
+                  "%s: totals give %lld / %lld workgroups and %lld packed bytes, the table %lld / %lld and %lld", who,
+                  (long long)totals->wg_fdct, (long long)totals->wg_mcu, (long long)totals->bits_cap,
+                  (long long)wg_fdct, (long long)wg_mcu, (long long)cap);
+  SP_JPEG_REQUIRE(work_bytes >= totals->work_bytes && bits_cap >= totals->bits_cap,
+                  "%s: buffers too small: work %lld < %lld or bits %lld < %lld bytes", who, (long long)work_bytes,
+                  (long long)totals->work_bytes, (long long)bits_cap, (long long)totals->bits_cap);
+  return 0;
+}
+
 }  // namespace jpeg_host
 }  // namespace sp

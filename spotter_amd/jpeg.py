@@ -13,6 +13,8 @@ keep the reference's host decode: UnsupportedJpeg is raised and open_image falls
 sp_jpeg_batch_to_rgb's two launches and one status readback per chunk of up to 64 files) with decode()'s outcome per
 file; spotter_amd/bulk.py builds the bulk pipeline on it. On an entropy="gpu" decoder the eligible
 files of a chunk are entropy-decoded on the device in one launch chain (sp_jpeg_entropy_batch_decode).
+`JpegEncoder.encode_many(srcs)` is the encode side of it: a chunk of up to 64 images in sp_jpeg_enc_batch_rgb's six
+launches, one readback and one download, every file what encode() returns.
 
 Opt-in (`JpegDecoder(device, entropy="gpu")`, or SPOTTER_JPEG_ENTROPY=gpu for the decoders open_image / image_module
 create): baseline files with one interleaved scan are entropy-decoded on the GPU too (sp_jpeg_entropy_pack on the
@@ -30,8 +32,8 @@ import numpy as np
 import torch
 
 from ._lib import (SP_JPEG_BATCH_MAX, SP_JPEG_NOT_ELIGIBLE, SP_JPEG_PKG_SMALL, SP_JPEG_UNSUPPORTED, SpJpegBatchItem,
-                   SpJpegBatchTotals, SpJpegEncLayout, SpJpegEntropyItem, SpJpegEntropyTotals, SpJpegLayout, SpJpegScan,
-                   lib)
+                   SpJpegBatchTotals, SpJpegEncBatchItem, SpJpegEncBatchTotals, SpJpegEncLayout, SpJpegEntropyItem,
+                   SpJpegEntropyTotals, SpJpegLayout, SpJpegScan, lib)
 from .config import check_jpeg_entropy, jpeg_entropy_from_env
 
 
@@ -73,11 +75,26 @@ _SEG_BYTES = 16
 # on one thread (32 files of 50-120 KB: 0.4 ms), so below this the pool's hand-offs cost more than they spread:
 # measured on 32 such files, decode_many ran 1.6-1.75x faster packing on the calling thread.
 PACK_POOL_BYTES = 1 << 24
+# encode buffers a JpegEncoder keeps between encode_many chunks; a chunk closes before it would pass one of them, and
+# a single image beyond one goes through encode(). The packed bit buffer is sized for the worst case (1676 bits a
+# block: 2 MiB for 640x640 at 4:2:0, 64 of them 128 MiB); the download takes only the bytes the device found in use.
+KEEP_ENC_WORK = 1 << 27  # bytes of encode workspace (coefficients, per-MCU counts and offsets) of a chunk
+KEEP_ENC_BITS = 1 << 28  # bytes of packed bit buffer of a chunk
+KEEP_ENC_PIX = 1 << 27   # bytes of host pixels (PIL sources) a chunk stages and uploads
+# Downloaded segment bytes of a chunk from which sp_jpeg_enc_finish (headers, 0xFF stuffing: a memchr / memcpy pass at
+# memory speed) runs in the thread pool; below it the hand-offs cost more than they spread, as with PACK_POOL_BYTES.
+FINISH_POOL_BYTES = 1 << 24
 
 
 def _new_batch_stats() -> dict:
     return {"calls": 0, "chunks": 0, "images": 0, "h2d_bytes": 0, "refused": 0, "flagged": 0, "gpu": 0, "host": 0,
             "fallback": {}}
+
+
+def _new_enc_stats() -> dict:
+    """encode_many's counters: calls, chunks, images encoded in chunks, images handed to encode() (beyond a kept-buffer
+    cap), bytes uploaded (table and host pixels) and downloaded (result and segments), stream waits."""
+    return {"calls": 0, "chunks": 0, "images": 0, "single": 0, "h2d_bytes": 0, "d2h_bytes": 0, "waits": 0}
 
 
 def _a16(v: int) -> int:
@@ -679,6 +696,11 @@ class JpegEncoder:
         self._stage = self._down = None
         self._nbits = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self._nbits_host = torch.zeros(1, dtype=torch.int64, pin_memory=True)
+        # encode_many: bit counts, segment offsets and bytes used of a chunk; the finish pool; the counters
+        self._res = torch.zeros(2 * SP_JPEG_BATCH_MAX + 1, dtype=torch.int64, device=self.dev)
+        self._res_host = torch.zeros(2 * SP_JPEG_BATCH_MAX + 1, dtype=torch.int64, pin_memory=True)
+        self._workers = None
+        self.stats = _new_enc_stats()
 
     def plan(self, W, H, quality=-1, subsampling=-1) -> SpJpegEncLayout:
         key = (W, H, quality, subsampling)
@@ -739,6 +761,130 @@ class JpegEncoder:
             if rc:
                 raise RuntimeError(f"sp_jpeg_enc_finish: {L.sp_last_error().decode(errors='replace')}")
             return out.raw[:n.value]
+
+    _pool = JpegDecoder._pool  # the same thread-pool helper, over this object's _workers
+
+    def _source(self, src, quality, subsampling):
+        """One encode_many source as the chunk code needs it: the layout, the device pointer (a tensor) or the host
+        pixels still to be staged (a PIL image), and what the chunk rule counts for it."""
+        s = types.SimpleNamespace(src=src, ptr=None, host=None, nbytes=0, keep=None)
+        if isinstance(src, DeviceRGBImage) and src._im is None:
+            s.src = src = src.spotter_device_rgb  # pending draws are flushed on the current stream
+        if isinstance(src, torch.Tensor):
+            assert src.dtype == torch.uint8 and src.is_cuda and src.dim() == 3 and src.shape[2] in (3, 4)
+            assert src.stride(2) == 1 and src.stride(1) == src.shape[2]
+            H, W, s.pb = src.shape
+            s.ptr, s.stride, s.keep = src.data_ptr(), src.stride(0), src
+        else:
+            W, H = src.size
+            s.host, s.stride, s.pb, s.keep = pil_pixels(src)
+            s.nbytes = s.stride * H
+        s.lay = self.plan(W, H, quality, subsampling)
+        s.need = ((s.lay.work_bytes + 255) & ~255, _a16(s.lay.bits_cap), (s.nbytes + 255) & ~255)
+        return s
+
+    def encode_many(self, srcs, quality=-1, subsampling=-1, comments=None, max_workers=None) -> list:
+        """encode() over a list of sources at one quality / subsampling: one file per source, byte for byte what
+        encode(src, quality, subsampling, comment) returns. srcs: uint8 [H, W, 3 | 4] device tensors (encode()'s stride
+        rules), DeviceRGBImages (pending draws are flushed first) and PIL RGB images, mixed freely; comments: None, or
+        one bytes / None per source.
+
+        Per chunk (up to SP_JPEG_BATCH_MAX images, closed earlier where its workspace, packed bit capacity or staged
+        host pixels would pass KEEP_ENC_WORK / KEEP_ENC_BITS / KEEP_ENC_PIX; a single image beyond one of them goes
+        through encode()): the host pixels of its PIL sources and the table staged into one pinned buffer and uploaded
+        with one copy, sp_jpeg_enc_batch_rgb's six launches on the current stream, one readback of the bit counts and
+        segment offsets, one download of exactly the bytes in use, then sp_jpeg_enc_finish per image (in a thread pool
+        of max_workers, default min(16, CPUs), from FINISH_POOL_BYTES of segment data on: ctypes releases the GIL).
+        Two stream waits per chunk where encode() makes two per image. `stats` counts what was done."""
+        srcs = list(srcs)
+        coms = [b""] * len(srcs) if comments is None else [c or b"" for c in comments]
+        if len(coms) != len(srcs):
+            raise ValueError("comments must be None or hold one entry per source")
+        workers = max_workers if max_workers is not None else default_decode_workers()
+        if workers < 1:
+            raise ValueError("max_workers must be at least 1")
+        self.stats["calls"] += 1
+        descs = [self._source(s, quality, subsampling) for s in srcs]
+        caps = (KEEP_ENC_WORK, KEEP_ENC_BITS, KEEP_ENC_PIX)
+        out = []
+        i = 0
+        while i < len(descs):
+            if any(x > cap for x, cap in zip(descs[i].need, caps)):
+                out.append(self.encode(descs[i].src, quality, subsampling, coms[i] or None))
+                self.stats["single"] += 1
+                i += 1
+                continue
+            n = _greedy([d.need for d in descs[i:i + SP_JPEG_BATCH_MAX]], caps)
+            with self._lock:
+                out += self._encode_chunk(lib(), descs[i:i + n], coms[i:i + n], workers)
+            i += n
+        return out
+
+    def _encode_chunk(self, L, descs, coms, workers):
+        n = len(descs)
+        cur = torch.cuda.current_stream(self.dev)
+        lays = (SpJpegEncLayout * n)(*[d.lay for d in descs])
+        items, totals = (SpJpegEncBatchItem * n)(), SpJpegEncBatchTotals()
+        _check(L.sp_jpeg_enc_batch_plan(lays, n, items, C.byref(totals)), "sp_jpeg_enc_batch_plan")
+        # the upload: [host pixels of the PIL sources, each at a multiple of 256][the table]
+        pix_off, tab_off = [], 0
+        for d in descs:
+            pix_off.append(tab_off)
+            tab_off += d.need[2]
+        nup = tab_off + C.sizeof(items)
+        self._stage = _grow(self._stage, nup, torch.uint8)
+        self._pix = _grow(self._pix, nup, torch.uint8, self.dev)
+        self._work = _grow(self._work, totals.work_bytes, torch.uint8, self.dev)
+        self._bits = _grow(self._bits, totals.bits_cap, torch.uint8, self.dev)
+        hp, dp = self._stage.data_ptr(), self._pix.data_ptr()
+        for it, d, off in zip(items, descs, pix_off):
+            if d.host is not None:
+                C.memmove(hp + off, d.host, d.nbytes)
+                d.keep = None
+            it.src = d.ptr if d.host is None else dp + off
+            it.row_stride, it.pixel_bytes = d.stride, d.pb
+        C.memmove(hp + tab_off, items, C.sizeof(items))
+        self._pix[:nup].copy_(self._stage[:nup], non_blocking=True)
+        _check(L.sp_jpeg_enc_batch_rgb(dp + tab_off, items, n, C.byref(totals), self._work.data_ptr(),
+                                       self._work.numel(), self._bits.data_ptr(), self._bits.numel(),
+                                       self._res.data_ptr(), cur.cuda_stream), "sp_jpeg_enc_batch_rgb")
+        m = 2 * n + 1
+        self._res_host[:m].copy_(self._res[:m], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        ev.synchronize()
+        res = self._res_host[:m].tolist()
+        nbits, seg, used = res[:n], res[n:2 * n], res[2 * n]
+        self._down = _grow(self._down, used, torch.uint8)
+        self._down[:used].copy_(self._bits[:used], non_blocking=True)
+        ev.record(cur)
+        ev.synchronize()
+        for d in descs:
+            d.keep = None
+        base = self._down.data_ptr()
+
+        def finish(k):
+            lay, com = descs[k].lay, coms[k]
+            cap = L.sp_jpeg_enc_max_bytes(C.byref(lay), nbits[k], len(com))
+            buf, cnt = C.create_string_buffer(cap), C.c_int64()
+            rc = L.sp_jpeg_enc_finish(C.byref(lay), base + seg[k], nbits[k], com, len(com), buf, cap, C.byref(cnt))
+            # the error text is thread-local: read where the call was made
+            return (rc, L.sp_last_error()) if rc else (0, C.string_at(buf, cnt.value))
+
+        if workers > 1 and n > 1 and used >= FINISH_POOL_BYTES:
+            done = list(self._pool(workers).map(finish, range(n)))
+        else:
+            done = [finish(k) for k in range(n)]
+        for rc, val in done:
+            if rc:
+                raise _error(rc, "sp_jpeg_enc_finish", val)
+        st = self.stats
+        st["chunks"] += 1
+        st["images"] += n
+        st["h2d_bytes"] += nup
+        st["d2h_bytes"] += 8 * m + used
+        st["waits"] += 2
+        return [val for _, val in done]
 
 
 _encoders: dict = {}

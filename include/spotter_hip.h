@@ -769,6 +769,40 @@ int sp_draw_rgb(uint8_t* rgb, int32_t height, int32_t width, int64_t row_stride,
                 const void* table_dev, int64_t table_bytes, void* stream);
 
 /*
+ * Batched label drawing (additive to ABI v20): the packed tables of up to SP_DRAW_BATCH_MAX images, each exactly as
+ * sp_draw_pack writes it, sit at 16-byte aligned offsets of one batch buffer (one H2D copy) and are applied by ONE
+ * launch whatever n is: one workgroup per touched tile of every image. One table row per image says where its pixels
+ * and its table lie and which workgroups are its own; a workgroup never spans two images and finds its row by the
+ * uniform binary search sp_jpeg_batch_to_rgb uses, then runs sp_draw_rgb's own device code on that image.
+ */
+#define SP_DRAW_BATCH_MAX 64 /* = SP_JPEG_BATCH_MAX: a decode / encode chunk is one draw batch */
+typedef struct {
+  uint8_t* rgb;            /* the image's pixels: an absolute device pointer (the images are separate tensors) */
+  int32_t height, width;
+  int64_t row_stride;      /* bytes between its rows, >= 3 * width */
+  int64_t table_off;       /* byte offset of its packed sp_draw_table in the batch buffer, a multiple of 16 */
+  int64_t table_bytes;     /* bytes of that table (>= its header's total_bytes) */
+  int32_t n_tiles;         /* its touched tiles = its workgroups, > 0 (the table header's n_tiles) */
+  int32_t first_wg;        /* its first workgroup in the launch: exclusive prefix sum of n_tiles */
+} sp_draw_batch_item;
+/* Host: read the n table headers at tables_host + items[i].table_off and fill items[i].n_tiles and first_wg (the
+ * other fields are the caller's and are left alone). Returns the launch's workgroup count (the sum of n_tiles), or
+ * -1 with a message: a NULL pointer, n outside [1, SP_DRAW_BATCH_MAX], a table_off that is negative, misaligned or
+ * leaves no room for a header in tables_bytes, a table without a touched tile (an image with nothing to draw is
+ * left out of the batch), more than 2^31 - 1 workgroups. No device call. */
+int64_t sp_draw_batch_plan(sp_draw_batch_item* items, int n, const void* tables_host, int64_t tables_bytes);
+/* Device: apply every row's table to its image, in place, in one launch. items_dev / tables_dev are the device
+ * copies (the caller's one H2D copy, ordered before this call on stream; items_dev 8-byte, tables_dev 16-byte
+ * aligned), items_host / tables_host the same bytes on the host, read here only to check the arguments before
+ * anything launches: n in [1, SP_DRAW_BATCH_MAX]; per row every check sp_draw_rgb makes of its image and table;
+ * table_off 16-byte aligned, [table_off, +table_bytes) inside tables_bytes and the ranges pairwise disjoint; n_tiles
+ * > 0 and the table header's; first_wg the exclusive prefix sum; the rows' pixel byte ranges pairwise disjoint (two
+ * rows over the same pixels would composite in no defined order). A refused call returns -1 and launches nothing.
+ * Asynchronous on `stream`; allocates nothing, makes no host-visible copy. */
+int sp_draw_batch_rgb(const sp_draw_batch_item* items_dev, const sp_draw_batch_item* items_host, int n,
+                      const void* tables_host, const void* tables_dev, int64_t tables_bytes, void* stream);
+
+/*
  * Cross-process batching (spotter_amd/shared_batch.py): the replica processes of one GPU hand their images to
  * one engine owner through host shared memory. Additive to ABI v20.
  *

@@ -156,6 +156,14 @@ class SpDrawTable(C.Structure):
     ]
 
 
+SP_DRAW_BATCH_MAX = 64
+
+
+class SpDrawBatchItem(C.Structure):
+    _fields_ = [("rgb", vp), ("height", i32), ("width", i32), ("row_stride", i64), ("table_off", i64),
+                ("table_bytes", i64), ("n_tiles", i32), ("first_wg", i32)]
+
+
 SP_COPY_MAX_SEGMENTS, SP_COPY_BLOCK_ELEMS = 64, 4096
 
 
@@ -252,6 +260,8 @@ _SIGS = {
                                     vp, i64, vp, vp]),
     "sp_draw_pack": (i32, [vp, i32, vp, i64, i32, i32, vp, i64, C.POINTER(i64)]),
     "sp_draw_rgb": (i32, [vp, i32, i32, i64, vp, vp, i64, vp]),
+    "sp_draw_batch_plan": (i64, [C.POINTER(SpDrawBatchItem), i32, vp, i64]),
+    "sp_draw_batch_rgb": (i32, [vp, C.POINTER(SpDrawBatchItem), i32, vp, vp, i64, vp]),
     "sp_host_register": (i32, [vp, i64, C.POINTER(vp)]),
     "sp_host_unregister": (i32, [vp]),
     "sp_copy_segments": (i32, [C.POINTER(SpCopySegmentsDesc), vp]),

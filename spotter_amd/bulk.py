@@ -17,14 +17,17 @@ runs processor → model → post_process_object_detection on the whole chunk. A
 does, so two RGB arenas are alive at a time. One process, two threads and the decode pool; a failure of the GPU step
 propagates as the exception it is.
 
-With labelled=True every result also carries "jpeg", the labelled image /detect returns (serve.py:119-142): stage C,
-at the end of stage B, draws each chunk image's boxes and texts in place on the device and encodes the chunk with one
-JpegEncoder.encode_many.
+With labelled=True every result also carries "jpeg", the labelled image /detect returns (serve.py:119-142): stage C
+records each chunk image's boxes and texts (spotter_amd/draw.py record_labels), applies the chunk's draws in place on
+the device with one launch and encodes the chunk, both inside one JpegEncoder.encode_many.
+With label_overlap=True stage C runs on a thread and stream of its own while stage B of the next chunk runs (off by
+default: measured no faster, §5.28).
 """
 from __future__ import annotations
 
 import argparse
 import concurrent.futures as cf
+import contextlib
 import io
 import json
 import os
@@ -71,15 +74,26 @@ class BulkDetector:
     (x0 + 5, y0 + 5) in white with a black stroke of 1, then the image saved as JPEG at Pillow's defaults with the
     source file's comment, as DeviceRGBImage.save writes it. A label_map key that is none of id2label's names is a
     ValueError. encoder: the JpegEncoder to use (default: the device's shared one), or anything with encode_many.
+    label_draw: "batched" records the labels with record_labels, so that encode_many applies a chunk's draws with one
+    launch; "pillow" makes the drop-in's ImageDraw calls and one sp_draw_rgb launch per image, as before §5.28.
+    label_overlap: stage C of chunk i runs on a worker thread with a stream of its own while the caller's thread runs
+    stage B of chunk i + 1 (its results are then yielded one stage B later); False: C runs at the end of B, on its
+    thread and stream. Both choices give the same results; the defaults are what measured faster: the batched draw
+    does, the overlap does not (both threads are Python-bound and share the interpreter lock).
     `stage_seconds` keeps the busy time of stage A and stage B of every chunk of the last detect() ("a" / "b",
     seconds), and with labelled=True that of the draw-plus-encode part ("c", not counted in "b")."""
 
     def __init__(self, model, processor, batch=32, threshold=0.5, decode_workers=None, decoder=None, device=None,
-                 jpeg_entropy="host", labelled=False, id2label=None, label_map=None, encoder=None):
+                 jpeg_entropy="host", labelled=False, id2label=None, label_map=None, encoder=None,
+                 label_draw="batched", label_overlap=False):
         from .config import check_jpeg_entropy
 
         if int(batch) < 1:
             raise ValueError("batch must be at least 1")
+        if label_draw not in ("batched", "pillow"):
+            raise ValueError("label_draw must be 'batched' or 'pillow'")
+        self.label_draw, self.label_overlap = label_draw, bool(label_overlap)
+        self._stream_c = None  # stage C's stream (label_overlap)
         if labelled and id2label is None:
             raise ValueError("labelled=True needs id2label (the model's config.id2label)")
         if label_map is not None and id2label is not None:
@@ -153,7 +167,7 @@ class BulkDetector:
         import torch
 
         t0 = time.perf_counter()
-        c = 0.0
+        work = None  # what stage C needs of this chunk
         keep = [k for k, im in enumerate(images) if im is not None]
         if keep:
             batch = [images[k] for k in keep]
@@ -173,35 +187,70 @@ class BulkDetector:
             for k, size, d in zip(keep, sizes, dets):
                 res[k] = {"size": size, "scores": d["scores"], "labels": d["labels"], "boxes": d["boxes"]}
             if self.labelled:
-                t1 = time.perf_counter()
-                self._stage_c(res, keep, batch, infos, gpu)
-                c = time.perf_counter() - t1
-                self.stage_seconds["c"].append(c)
-        self.stage_seconds["b"].append(time.perf_counter() - t0 - c)
+                fwd = None
+                if gpu is not None and self.label_overlap:
+                    # the forward's reads of the chunk's pixels are enqueued: stage C's stream draws after them
+                    fwd = torch.cuda.Event()
+                    fwd.record(cur)
+                work = (keep, batch, infos, fwd)
+        self.stage_seconds["b"].append(time.perf_counter() - t0)
+        return res, work
+
+    # -- stage C: draw and encode, after stage B of its chunk -------------------------------------------------
+    def _stage_c(self, res, work, gpu):
+        """Stage C of one chunk, timed, on the calling thread: B's own (its current stream), or with label_overlap the
+        worker's, where it runs on stage C's stream behind the event B recorded after the forward."""
+        t0 = time.perf_counter()
+        keep, batch, infos, fwd = work
+        if fwd is None:
+            self._label_chunk(res, keep, batch, infos, gpu)
+        else:
+            import torch
+
+            dev = gpu[0]
+            if self._stream_c is None:
+                self._stream_c = torch.cuda.Stream(dev)
+            sc = self._stream_c
+            with torch.cuda.device(dev), torch.cuda.stream(sc):
+                sc.wait_event(fwd)
+                for im in batch:
+                    if torch.is_tensor(im) and im.is_cuda:
+                        im.record_stream(sc)  # the arena is A's, read on B's stream and drawn on here
+                self._label_chunk(res, keep, batch, infos, gpu)
+        self.stage_seconds["c"].append(time.perf_counter() - t0)
         return res
 
-    # -- stage C: draw and encode, at the end of stage B ------------------------------------------------------
-    def _stage_c(self, res, keep, batch, infos, gpu):
-        """serve.py:119-142 over the chunk: the draws through the drop-in's ImageDraw on a DeviceRGBImage over the
-        chunk's own pixels (in place: the forward has read them on this stream, and the arena is the chunk's), then
-        one encode_many. An image whose save the GPU encoder does not take (an unusual comment) is saved on its own,
-        by the rule DeviceRGBImage.save applies."""
-        from .draw import draw_module
+    def _label_chunk(self, res, keep, batch, infos, gpu):
+        """serve.py:119-142 over the chunk: the labels recorded on a DeviceRGBImage over the chunk's own pixels (drawn
+        in place: the forward has read them, and the arena is the chunk's), then one encode_many, which applies the
+        chunk's draws with one launch. An image whose save the GPU encoder does not take (an unusual comment) is saved
+        on its own, by the rule DeviceRGBImage.save applies."""
+        from .draw import draw_module, record_labels
         from .jpeg import _gpu_jpeg_options
 
         draw_mod = draw_module()
         pictures = []
         for k, im in zip(keep, batch):
             picture = self._picture(im, infos[k], gpu)
-            draw = draw_mod.Draw(picture)
+            boxes, texts = [], []
             for lab, box in zip(res[k]["labels"].tolist(), res[k]["boxes"].tolist()):
                 text = self.id2label[int(lab)]
                 if self.label_map is not None:
                     if text not in self.label_map:
                         continue
                     text = self.label_map[text]
-                draw.rectangle(box, outline="red", width=3)
-                draw.text(xy=(box[0] + 5, box[1] + 5), text=text, fill="white", stroke_width=1, stroke_fill="black")
+                boxes.append(box)
+                texts.append(text)
+            if self.label_draw == "batched":
+                record_labels(picture, boxes, texts)
+            else:
+                draw = draw_mod.Draw(picture)
+                for box, text in zip(boxes, texts):
+                    draw.rectangle(box, outline="red", width=3)
+                    draw.text(xy=(box[0] + 5, box[1] + 5), text=text, fill="white", stroke_width=1,
+                              stroke_fill="black")
+                if hasattr(picture, "flush"):
+                    picture.flush()  # one sp_draw_rgb launch per image, as before encode_many batched the draws
             pictures.append(picture)
         opts = [_gpu_jpeg_options(p, io.BytesIO(), "JPEG", {}) for p in pictures]
         together = [i for i, o in enumerate(opts) if o is not None]
@@ -256,13 +305,33 @@ class BulkDetector:
         if not chunk:
             return
         gpu = self._gpu()
-        with cf.ThreadPoolExecutor(max_workers=1, thread_name_prefix="spotter-bulk") as ex:
+        overlap = self.labelled and self.label_overlap
+        with contextlib.ExitStack() as stack:  # (leaving it, an early close() included, joins the threads)
+            ex = stack.enter_context(cf.ThreadPoolExecutor(max_workers=1, thread_name_prefix="spotter-bulk"))
+            ex_c = stack.enter_context(cf.ThreadPoolExecutor(max_workers=1, thread_name_prefix="spotter-bulk-c")) \
+                if overlap else None
             fut = ex.submit(self._stage_a, chunk, gpu)
-            while fut is not None:
-                res, images, event, infos = fut.result()
-                chunk = take()
-                fut = ex.submit(self._stage_a, chunk, gpu) if chunk else None
-                yield from self._stage_b(res, images, event, gpu, infos)
+            before = None  # label_overlap: the previous chunk's stage C, yielded after this chunk's stage B
+            try:
+                while fut is not None:
+                    res, images, event, infos = fut.result()
+                    chunk = take()
+                    fut = ex.submit(self._stage_a, chunk, gpu) if chunk else None
+                    res, work = self._stage_b(res, images, event, gpu, infos)
+                    if ex_c is None:
+                        if work is not None:
+                            self._stage_c(res, work, gpu)
+                        yield from res
+                        continue
+                    now = ex_c.submit(self._stage_c, res, work, gpu) if work is not None else res
+                    if before is not None:
+                        yield from (before.result() if isinstance(before, cf.Future) else before)
+                    before = now
+                if before is not None:
+                    yield from (before.result() if isinstance(before, cf.Future) else before)
+            finally:
+                if ex_c is not None:
+                    ex_c.shutdown(wait=True, cancel_futures=True)  # nothing new starts after an error or a close()
 
 
 def walk(paths):

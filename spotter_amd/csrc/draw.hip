@@ -42,9 +42,11 @@ __device__ __forceinline__ uint32_t blend8(uint32_t m, uint32_t out, uint32_t in
   return ((t >> 8) + t) >> 8;
 }
 
-__global__ __launch_bounds__(kThreads) void draw_kernel(const DrawArgs a) {
-  SP_BCHECK(blockIdx.x, a.n_tiles);
-  const sp_draw_tile tile = a.tiles[blockIdx.x];
+// One workgroup's work: touched tile `t` of the image `a` describes. Shared by the single-image and the batched kernel,
+// so both write the same pixels by construction.
+__device__ __forceinline__ void draw_tile(const DrawArgs& a, const int t) {
+  SP_BCHECK(t, a.n_tiles);
+  const sp_draw_tile tile = a.tiles[t];
   const int y = tile.ty * kTileH + (int)threadIdx.x / (kTileW / kPix);
   const int x = tile.tx * kTileW + ((int)threadIdx.x % (kTileW / kPix)) * kPix;
   if (y >= a.h || x >= a.w) return;
@@ -113,6 +115,34 @@ __global__ __launch_bounds__(kThreads) void draw_kernel(const DrawArgs a) {
     for (int i = 0; i < kPix * 3; ++i)
       if (i < npx * 3) p[i] = (uint8_t)c[i];
   }
+}
+
+__global__ __launch_bounds__(kThreads) void draw_kernel(const DrawArgs a) { draw_tile(a, (int)blockIdx.x); }
+
+// The batch: the workgroup finds its image's row (uniform binary search over first_wg), builds that image's DrawArgs
+// from the row and from the table header at tables + table_off (both uniform across the workgroup: scalar loads) and
+// runs the single-image body on its own tile of it. The extents SP_BCHECK sees are the image's own, not the buffer's.
+__global__ __launch_bounds__(kThreads) void draw_batch_kernel(const sp_draw_batch_item* __restrict__ items, const int n,
+                                                              const uint8_t* __restrict__ tables) {
+  const int img = batch_image(items, n, &sp_draw_batch_item::first_wg, (int)blockIdx.x);
+  SP_BCHECK(img, n);
+  const sp_draw_batch_item it = items[img];
+  const uint8_t* tb = tables + it.table_off;
+  const sp_draw_table hd = *reinterpret_cast<const sp_draw_table*>(tb);
+  DrawArgs a;
+  a.rgb = it.rgb;
+  a.h = it.height;
+  a.w = it.width;
+  a.stride = it.row_stride;
+  a.ops = reinterpret_cast<const sp_draw_op*>(tb + hd.ops_off);
+  a.tiles = reinterpret_cast<const sp_draw_tile*>(tb + hd.tiles_off);
+  a.refs = reinterpret_cast<const int32_t*>(tb + hd.refs_off);
+  a.masks = tb + hd.masks_off;
+  a.n_ops = hd.n_ops;
+  a.n_tiles = hd.n_tiles;
+  a.n_refs = hd.n_refs;
+  a.mask_bytes = hd.mask_bytes;
+  draw_tile(a, (int)blockIdx.x - it.first_wg);
 }
 
 inline int64_t align16(int64_t v) { return (v + 15) & ~int64_t(15); }
@@ -187,20 +217,22 @@ extern "C" int sp_draw_pack(const sp_draw_op* ops, int32_t n_ops, const uint8_t*
   return 0;
 }
 
-extern "C" int sp_draw_rgb(uint8_t* rgb, int32_t height, int32_t width, int64_t row_stride, const void* table_host,
-                           const void* table_dev, int64_t table_bytes, void* stream) {
+// Every check sp_draw_rgb and sp_draw_batch_rgb make of one image and the host copy of its packed table before
+// anything launches; *out is the table's header. `fn` names the entry point in the message.
+static int check_table(const char* fn, const uint8_t* rgb, int32_t height, int32_t width, int64_t row_stride,
+                       const void* table_host, int64_t table_bytes, sp_draw_table* out) {
   using namespace sp;
-  SP_ARG_CHECK(rgb && table_host && table_dev, "sp_draw_rgb: null args");
-  SP_ARG_CHECK(height > 0 && width > 0 && row_stride >= (int64_t)3 * width, "sp_draw_rgb: bad image %dx%d stride %lld",
+  SP_ARG_CHECK(rgb && table_host, "%s: null args", fn);
+  SP_ARG_CHECK(height > 0 && width > 0 && row_stride >= (int64_t)3 * width, "%s: bad image %dx%d stride %lld", fn,
                width, height, (long long)row_stride);
-  SP_ARG_CHECK(table_bytes >= (int64_t)sizeof(sp_draw_table), "sp_draw_rgb: table shorter than its header");
+  SP_ARG_CHECK(table_bytes >= (int64_t)sizeof(sp_draw_table), "%s: table shorter than its header", fn);
   sp_draw_table hd;
   memcpy(&hd, table_host, sizeof(hd));
-  SP_ARG_CHECK(hd.height == height && hd.width == width, "sp_draw_rgb: table packed for %dx%d, image is %dx%d",
-               hd.width, hd.height, width, height);
+  SP_ARG_CHECK(hd.height == height && hd.width == width, "%s: table packed for %dx%d, image is %dx%d", fn, hd.width,
+               hd.height, width, height);
   SP_ARG_CHECK(hd.n_ops >= 0 && hd.n_tiles >= 0 && hd.n_refs >= 0 && hd.mask_bytes >= 0 &&
                    hd.total_bytes <= table_bytes,
-               "sp_draw_rgb: bad table counts");
+               "%s: bad table counts", fn);
   auto section = [&](int64_t off, int64_t bytes) {
     return off >= (int64_t)sizeof(sp_draw_table) && off % 16 == 0 && bytes >= 0 && off <= hd.total_bytes &&
            bytes <= hd.total_bytes - off;
@@ -208,23 +240,23 @@ extern "C" int sp_draw_rgb(uint8_t* rgb, int32_t height, int32_t width, int64_t 
   SP_ARG_CHECK(section(hd.ops_off, (int64_t)hd.n_ops * sizeof(sp_draw_op)) &&
                    section(hd.tiles_off, (int64_t)hd.n_tiles * sizeof(sp_draw_tile)) &&
                    section(hd.refs_off, (int64_t)hd.n_refs * sizeof(int32_t)) && section(hd.masks_off, hd.mask_bytes),
-               "sp_draw_rgb: a table section lies outside the table");
+               "%s: a table section lies outside the table", fn);
   const uint8_t* hb = static_cast<const uint8_t*>(table_host);
   const sp_draw_op* ops = reinterpret_cast<const sp_draw_op*>(hb + hd.ops_off);
   const sp_draw_tile* tiles = reinterpret_cast<const sp_draw_tile*>(hb + hd.tiles_off);
   const int32_t* refs = reinterpret_cast<const int32_t*>(hb + hd.refs_off);
   for (int i = 0; i < hd.n_ops; ++i) {
     const sp_draw_op& o = ops[i];
-    SP_ARG_CHECK(o.kind == SP_DRAW_FILL || o.kind == SP_DRAW_BLEND, "sp_draw_rgb: operation %d has kind %d", i, o.kind);
+    SP_ARG_CHECK(o.kind == SP_DRAW_FILL || o.kind == SP_DRAW_BLEND, "%s: operation %d has kind %d", fn, i, o.kind);
     SP_ARG_CHECK(o.x0 >= 0 && o.x0 <= o.x1 && o.x1 < width && o.y0 >= 0 && o.y0 <= o.y1 && o.y1 < height,
-                 "sp_draw_rgb: operation %d (%d, %d)-(%d, %d) outside the %dx%d image", i, o.x0, o.y0, o.x1, o.y1,
-                 width, height);
+                 "%s: operation %d (%d, %d)-(%d, %d) outside the %dx%d image", fn, i, o.x0, o.y0, o.x1, o.y1, width,
+                 height);
     if (o.kind == SP_DRAW_BLEND) {
       // first and last mask byte the rectangle reads (rows sy .. sy + y1 - y0, columns sx .. sx + x1 - x0)
       SP_ARG_CHECK(o.mask_stride >= 0 && o.sx >= 0 && o.sy >= 0 && o.mask_off >= 0 && o.mask_off <= hd.mask_bytes,
-                   "sp_draw_rgb: operation %d has a negative mask field", i);
+                   "%s: operation %d has a negative mask field", fn, i);
       const int64_t last = o.mask_off + ((int64_t)o.sy + (o.y1 - o.y0)) * o.mask_stride + o.sx + (o.x1 - o.x0);
-      SP_ARG_CHECK(last < hd.mask_bytes, "sp_draw_rgb: operation %d reads mask byte %lld of %lld", i, (long long)last,
+      SP_ARG_CHECK(last < hd.mask_bytes, "%s: operation %d reads mask byte %lld of %lld", fn, i, (long long)last,
                    (long long)hd.mask_bytes);
     }
   }
@@ -232,20 +264,30 @@ extern "C" int sp_draw_rgb(uint8_t* rgb, int32_t height, int32_t width, int64_t 
   int64_t next = 0, prev_key = -1;
   for (int t = 0; t < hd.n_tiles; ++t) {
     const sp_draw_tile& tl = tiles[t];
-    SP_ARG_CHECK(tl.tx >= 0 && tl.tx < tw && tl.ty >= 0 && tl.ty < th, "sp_draw_rgb: tile %d (%d, %d) outside the image",
-                 t, tl.tx, tl.ty);
+    SP_ARG_CHECK(tl.tx >= 0 && tl.tx < tw && tl.ty >= 0 && tl.ty < th, "%s: tile %d (%d, %d) outside the image", fn, t,
+                 tl.tx, tl.ty);
     const int64_t key = (int64_t)tl.ty * tw + tl.tx;
-    SP_ARG_CHECK(key > prev_key, "sp_draw_rgb: tile %d repeats or is out of order", t);
+    SP_ARG_CHECK(key > prev_key, "%s: tile %d repeats or is out of order", fn, t);
     prev_key = key;
     SP_ARG_CHECK(tl.count > 0 && tl.first == next && (int64_t)tl.first + tl.count <= hd.n_refs,
-                 "sp_draw_rgb: tile %d has an unordered reference range [%d, +%d)", t, tl.first, tl.count);
+                 "%s: tile %d has an unordered reference range [%d, +%d)", fn, t, tl.first, tl.count);
     next = (int64_t)tl.first + tl.count;
     for (int r = tl.first; r < tl.first + tl.count; ++r) {
-      SP_ARG_CHECK(refs[r] >= 0 && refs[r] < hd.n_ops, "sp_draw_rgb: tile %d references operation %d of %d", t, refs[r],
+      SP_ARG_CHECK(refs[r] >= 0 && refs[r] < hd.n_ops, "%s: tile %d references operation %d of %d", fn, t, refs[r],
                    hd.n_ops);
-      SP_ARG_CHECK(r == tl.first || refs[r] > refs[r - 1], "sp_draw_rgb: tile %d lists its operations out of order", t);
+      SP_ARG_CHECK(r == tl.first || refs[r] > refs[r - 1], "%s: tile %d lists its operations out of order", fn, t);
     }
   }
+  *out = hd;
+  return 0;
+}
+
+extern "C" int sp_draw_rgb(uint8_t* rgb, int32_t height, int32_t width, int64_t row_stride, const void* table_host,
+                           const void* table_dev, int64_t table_bytes, void* stream) {
+  using namespace sp;
+  SP_ARG_CHECK(table_dev, "sp_draw_rgb: null args");
+  sp_draw_table hd;
+  if (check_table("sp_draw_rgb", rgb, height, width, row_stride, table_host, table_bytes, &hd)) return -1;
   if (hd.n_tiles == 0) return 0;
   const uint8_t* db = static_cast<const uint8_t*>(table_dev);
   DrawArgs a;
@@ -263,4 +305,80 @@ extern "C" int sp_draw_rgb(uint8_t* rgb, int32_t height, int32_t width, int64_t 
   a.mask_bytes = hd.mask_bytes;
   hipLaunchKernelGGL(draw_kernel, dim3(hd.n_tiles), dim3(kThreads), 0, as_stream(stream), a);
   return check_launch("sp_draw_rgb");
+}
+
+extern "C" int64_t sp_draw_batch_plan(sp_draw_batch_item* items, int n, const void* tables_host,
+                                      int64_t tables_bytes) {
+  using namespace sp;
+  SP_ARG_CHECK(items && tables_host, "sp_draw_batch_plan: null args");
+  SP_ARG_CHECK(n >= 1 && n <= SP_DRAW_BATCH_MAX, "sp_draw_batch_plan: n = %d outside [1, %d]", n, SP_DRAW_BATCH_MAX);
+  int64_t wg = 0;
+  for (int i = 0; i < n; ++i) {
+    const int64_t off = items[i].table_off;
+    SP_ARG_CHECK(off >= 0 && off % 16 == 0 && tables_bytes >= (int64_t)sizeof(sp_draw_table) &&
+                     off <= tables_bytes - (int64_t)sizeof(sp_draw_table),
+                 "sp_draw_batch_plan: image %d: table offset %lld misaligned or outside the %lld-byte buffer", i,
+                 (long long)off, (long long)tables_bytes);
+    sp_draw_table hd;
+    memcpy(&hd, static_cast<const uint8_t*>(tables_host) + off, sizeof(hd));
+    SP_ARG_CHECK(hd.n_tiles > 0, "sp_draw_batch_plan: image %d: its table has %d touched tiles", i, hd.n_tiles);
+    wg += hd.n_tiles;
+    SP_ARG_CHECK(wg < (int64_t(1) << 31), "sp_draw_batch_plan: more than 2^31 - 1 workgroups");
+  }
+  wg = 0;
+  for (int i = 0; i < n; ++i) {  // (written only once every row has passed)
+    sp_draw_table hd;
+    memcpy(&hd, static_cast<const uint8_t*>(tables_host) + items[i].table_off, sizeof(hd));
+    items[i].n_tiles = hd.n_tiles;
+    items[i].first_wg = (int32_t)wg;
+    wg += hd.n_tiles;
+  }
+  return wg;
+}
+
+extern "C" int sp_draw_batch_rgb(const sp_draw_batch_item* items_dev, const sp_draw_batch_item* items_host, int n,
+                                 const void* tables_host, const void* tables_dev, int64_t tables_bytes,
+                                 void* stream) {
+  using namespace sp;
+  SP_ARG_CHECK(items_dev && items_host && tables_host && tables_dev, "sp_draw_batch_rgb: null args");
+  SP_ARG_CHECK(n >= 1 && n <= SP_DRAW_BATCH_MAX, "sp_draw_batch_rgb: n = %d outside [1, %d]", n, SP_DRAW_BATCH_MAX);
+  SP_ARG_CHECK(reinterpret_cast<uintptr_t>(items_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(tables_dev) % 16 == 0,
+               "sp_draw_batch_rgb: misaligned device table");
+  int64_t wg = 0;
+  for (int i = 0; i < n; ++i) {
+    const sp_draw_batch_item& it = items_host[i];
+    SP_ARG_CHECK(it.table_off >= 0 && it.table_off % 16 == 0 && it.table_bytes >= 0 && it.table_off <= tables_bytes &&
+                     it.table_bytes <= tables_bytes - it.table_off,
+                 "sp_draw_batch_rgb: image %d: table range [%lld, +%lld) misaligned or outside the %lld-byte buffer", i,
+                 (long long)it.table_off, (long long)it.table_bytes, (long long)tables_bytes);
+    sp_draw_table hd;
+    if (check_table("sp_draw_batch_rgb", it.rgb, it.height, it.width, it.row_stride,
+                    static_cast<const uint8_t*>(tables_host) + it.table_off, it.table_bytes, &hd)) {
+      char msg[400];
+      snprintf(msg, sizeof(msg), "%s", sp_last_error());
+      set_error("image %d: %s", i, msg);
+      return -1;
+    }
+    SP_ARG_CHECK(it.n_tiles > 0 && it.n_tiles == hd.n_tiles,
+                 "sp_draw_batch_rgb: image %d: n_tiles %d, its table has %d (an image without draws is left out)", i,
+                 it.n_tiles, hd.n_tiles);
+    SP_ARG_CHECK(it.first_wg == wg, "sp_draw_batch_rgb: image %d: first_wg %d is not the prefix sum %lld", i,
+                 it.first_wg, (long long)wg);
+    wg += it.n_tiles;
+    SP_ARG_CHECK(wg < (int64_t(1) << 31), "sp_draw_batch_rgb: more than 2^31 - 1 workgroups");
+    // pairwise disjoint table ranges and pixel byte ranges (n <= 64: the quadratic check is a few thousand compares)
+    const uintptr_t p0 = reinterpret_cast<uintptr_t>(it.rgb);
+    const uintptr_t p1 = p0 + (uintptr_t)((int64_t)(it.height - 1) * it.row_stride + (int64_t)3 * it.width);
+    for (int j = 0; j < i; ++j) {
+      const sp_draw_batch_item& o = items_host[j];
+      SP_ARG_CHECK(it.table_off + it.table_bytes <= o.table_off || o.table_off + o.table_bytes <= it.table_off,
+                   "sp_draw_batch_rgb: the tables of images %d and %d overlap", j, i);
+      const uintptr_t q0 = reinterpret_cast<uintptr_t>(o.rgb);
+      const uintptr_t q1 = q0 + (uintptr_t)((int64_t)(o.height - 1) * o.row_stride + (int64_t)3 * o.width);
+      SP_ARG_CHECK(p1 <= q0 || q1 <= p0, "sp_draw_batch_rgb: images %d and %d share pixel bytes", j, i);
+    }
+  }
+  hipLaunchKernelGGL(draw_batch_kernel, dim3((unsigned)wg), dim3(kThreads), 0, as_stream(stream), items_dev, n,
+                     static_cast<const uint8_t*>(tables_dev));
+  return check_launch("sp_draw_batch_rgb");
 }

@@ -30,6 +30,7 @@ import types
 from collections import OrderedDict
 
 from PIL import Image as _PILImage
+from PIL import ImageColor as _PILColor
 from PIL import ImageDraw as _PILDraw
 from PIL import ImageFont as _PILFont
 from PIL import ImagePath as _PILPath
@@ -95,6 +96,33 @@ class _MemoFont(_PILFont.FreeTypeFont):
         return b
 
     def getmask2(self, text, mode="", *args, start=None, **kwargs):
+        out = self._getmask2(text, mode, *args, start=start, **kwargs)
+        log = getattr(_capturing, "calls", None)
+        if log is not None:  # record_labels is learning a stamp on this thread
+            log.append((text, mode, args, start, kwargs, out))
+        return out
+
+    def lookup(self, text, mode, sx, sy, cx, cy, opts):
+        """What getmask2(text, mode, start=(sx, sy), **kwargs) returns when it needs no render, else None: the same
+        two lookups in the same order with the same bookkeeping, for a caller that already holds the key's parts
+        (opts = _opts(kwargs), (cx, cy) the start classes, neither None; mode "", "L" or "1")."""
+        ekey = (text, mode, sx, sy, opts)
+        with self._memo_lock:
+            hit = self._exact.get(ekey)
+            if hit is not None:
+                self._exact.move_to_end(ekey)
+        if hit is not None:
+            self.memo_stats["exact_hits"] += 1
+            return hit
+        key = (text, mode, cx, cy, opts)
+        if key in self._no_memo:
+            return None
+        hit = self._memo.get(key)
+        if hit is not None:
+            self.memo_stats["hits"] += 1
+        return hit
+
+    def _getmask2(self, text, mode="", *args, start=None, **kwargs):
         if mode not in ("", "L", "1"):
             # "RGBA" (ImageDraw.text(embedded_color=True)): Pillow fills the returned mask's alpha band in place
             # (color.fillband), so a shared cached mask would be overwritten; these renders are never cached
@@ -103,7 +131,7 @@ class _MemoFont(_PILFont.FreeTypeFont):
         key = ekey = None
         if not args and isinstance(text, str) and start is not None:
             try:
-                opts = tuple(sorted((k, tuple(v) if isinstance(v, list) else v) for k, v in kwargs.items()))
+                opts = _opts(kwargs)
                 sx, sy = float(start[0]), float(start[1])
                 ekey = (text, mode, sx, sy, opts)
                 hash(ekey)
@@ -148,6 +176,13 @@ class _MemoFont(_PILFont.FreeTypeFont):
                     self._no_memo.add(key)
                 del self._pending[key]
         return mask, offset
+
+
+def _opts(kwargs) -> tuple:
+    return tuple(sorted((k, tuple(v) if isinstance(v, list) else v) for k, v in kwargs.items()))
+
+
+_capturing = threading.local()  # .calls: the getmask2 calls of this thread's running stamp capture, else absent
 
 
 def _tobytes(mask) -> bytes:
@@ -288,6 +323,19 @@ def _ints(xy, n):
     return out
 
 
+def _outline(lst, x0, y0, x1, y1, ink, w):
+    """ImagingDrawRectangle, outline of width w > 0, as four fills: for i < w the rows y0 + i and y1 - i over x0..x1,
+    then the columns x1 - i and x0 + i from row y0 + w towards row y1 - w + 1, half-open in the direction of travel
+    (Draw.c line32 draws |dy| points from the start). One ink, so the order among the four pieces does not matter."""
+    lst.fill(x0, y0, x1, y0 + w - 1, ink)
+    lst.fill(x0, y1 - w + 1, x1, y1, ink)
+    ys, ye = y0 + w, y1 - w + 1
+    if ye != ys:
+        ra, rb = (ys, ye - 1) if ye > ys else (ye + 1, ys)
+        lst.fill(x1 - w + 1, ra, x1, rb, ink)
+        lst.fill(x0, ra, x0 + w - 1, rb, ink)
+
+
 class _Recorder:
     """Stands where ImageDraw keeps its C core draw object. draw_rectangle and draw_bitmap append to the image's
     draw list by Pillow's rules (Draw.c ImagingDrawRectangle, Paste.c ImagingFill2); every other method hands the
@@ -312,16 +360,7 @@ class _Recorder:
         w = width or 1
         if w < 0:
             return
-        # ImagingDrawRectangle, outline: for i < w the rows y0 + i and y1 - i over x0..x1, then the columns x1 - i
-        # and x0 + i from row y0 + w towards row y1 - w + 1, half-open in the direction of travel (Draw.c line32
-        # draws |dy| points from the start). One ink, so the order among the four pieces does not matter.
-        lst.fill(x0, y0, x1, y0 + w - 1, ink)
-        lst.fill(x0, y1 - w + 1, x1, y1, ink)
-        ys, ye = y0 + w, y1 - w + 1
-        if ye != ys:
-            ra, rb = (ys, ye - 1) if ye > ys else (ye + 1, ys)
-            lst.fill(x1 - w + 1, ra, x1, rb, ink)
-            lst.fill(x0, ra, x0 + w - 1, rb, ink)
+        _outline(lst, x0, y0, x1, y1, ink, w)
 
     def draw_bitmap(self, xy, mask, ink):
         if type(xy) is tuple and len(xy) == 2 and type(xy[0]) is int and type(xy[1]) is int:
@@ -373,6 +412,149 @@ class DeviceDraw(_PILDraw.ImageDraw):
             self._image.load()
             self.draw = _PILImage.core.draw(self._image.im, 0)
         return self.draw
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# record_labels: the labels of serve.py:128-136 recorded without Pillow's Python half where that is
+# known to give the same list. ImageDraw.text spends its time between the call and the two things that matter here:
+# what it asks the font for (getmask2) and what it hands the core object (draw_bitmap). A *stamp* is that pair as
+# observed on a real DeviceDraw.text call for one (string, start class pair): per blend the font call (string, mode,
+# options; its start is the fractional start) and the offset it returned, the bitmap's position relative to
+# (int(x), int(y)) and the ink. Nothing about how ImageDraw.text is written is assumed: a capture whose calls do not
+# have exactly that shape is not a stamp, a key is stamped only after two captures at different fractions of its
+# class gave the same stamp, and a key whose captures differ is never stamped. A stamp is replayed by asking the font
+# again (a memo lookup: the very mask object, so also the very bytes object, that Pillow's path would have blended,
+# which keeps the list's one-copy-per-mask rule) and calling DrawList.blend as _Recorder.draw_bitmap does.
+
+
+class _Capture(_Recorder):
+    """The recorder of record_labels' DeviceDraw: during a capture it also notes what draw_bitmap received."""
+
+    seen = None
+
+    def draw_bitmap(self, xy, mask, ink):
+        if self.seen is not None:
+            self.seen.append((xy, mask, ink))
+        return super().draw_bitmap(xy, mask, ink)
+
+
+_stamps: dict = {}       # (text, cx, cy) -> trusted stamp
+_stamp_first: dict = {}  # key -> ((fx, fy), stamp) of its first capture
+_stamp_never: set = set()
+_stamp_lock = threading.Lock()
+stamp_stats = {"hits": 0, "captures": 0, "fallbacks": 0}
+_TEXT = {"fill": "white", "stroke_width": 1, "stroke_fill": "black"}  # serve.py:131-136
+
+
+def _capture_text(draw, x, y, fx, fy, text):
+    """DeviceDraw.text for one label, for real (draw.draw is record_labels' _Capture), and the stamp it amounts to
+    (None where the image was handed over to Pillow or the calls made are not of the shape a stamp replays)."""
+    rec = draw.draw
+    calls, seen = [], []
+    rec.seen, _capturing.calls = seen, calls
+    try:
+        draw.text(xy=(x, y), text=text, **_TEXT)
+    finally:
+        rec.seen = _capturing.calls = None
+    if draw._image._im is not None or len(calls) != len(seen) or not seen:
+        return None
+    ix, iy = int(x), int(y)
+    stamp = []
+    for (t, mode, args, start, kw, out), (xy, mask, ink) in zip(calls, seen):
+        if (args or type(start) is not tuple or start != (fx, fy) or type(out) is not tuple or len(out) != 2
+                or out[0] is not mask or getattr(mask, "mode", None) != "L" or type(ink) is not int
+                or type(xy) is not tuple or len(xy) != 2 or type(xy[0]) is not int or type(xy[1]) is not int
+                or abs(xy[0] - ix) >= 1 << 20 or abs(xy[1] - iy) >= 1 << 20):
+            return None
+        try:
+            opts = _opts(kw)
+            hash(opts)
+        except TypeError:
+            return None
+        if type(t) is not str or mode not in ("", "L", "1"):
+            return None
+        stamp.append((t, mode, dict(kw), tuple(out[1]), xy[0] - ix, xy[1] - iy, ink, opts))
+    return tuple(stamp)
+
+
+def _replay(lst, font, stamp, ix, iy, start, cx, cy) -> bool:
+    """Append a stamp's blends at (ix, iy). False, with nothing appended, where the font's answer is not the stamp's."""
+    got = []
+    for t, mode, kw, offset, _, _, _, opts in stamp:
+        hit = font.lookup(t, mode, start[0], start[1], cx, cy, opts)
+        mask, off = font.getmask2(t, mode, start=start, **kw) if hit is None else hit
+        if tuple(off) != offset or mask.mode != "L":
+            return False
+        got.append(mask)
+    for mask, (_, _, _, _, dx, dy, ink, _) in zip(got, stamp):
+        mw, mh = mask.size
+        lst.blend(ix + dx, iy + dy, _bytes_of(mask), mw, mh, ink)
+    return True
+
+
+def record_labels(image, boxes, texts) -> None:
+    """serve.py:128-136 for one image: per detection `rectangle(box, outline="red", width=3)` then
+    `text((box[0] + 5, box[1] + 5), text, fill="white", stroke_width=1, stroke_fill="black")`. On a device image
+    without host pixels, `image._draw_list` afterwards holds byte for byte the operations, and the same mask bytes at
+    the same offsets, that those calls through draw_module().Draw(image) would have appended: each detection takes
+    either a fast path (the rectangle's four fills straight from the box; the text from a trusted stamp) or the
+    DeviceDraw calls themselves, and which one is never visible in the list. Any other image is drawn on through
+    draw_module().Draw(image). `stamp_stats` counts the texts replayed from a stamp ("hits"), recorded through
+    Pillow while their key was being learned ("captures") and recorded through Pillow for good ("fallbacks")."""
+    import math
+
+    draw = draw_module().Draw(image)
+    if type(draw) is not DeviceDraw:
+        for box, text in zip(boxes, texts):
+            draw.rectangle(box, outline="red", width=3)
+            draw.text(xy=(box[0] + 5, box[1] + 5), text=text, **_TEXT)
+        return
+    draw.draw = _Capture(draw)
+    lst = image._draw_list
+    font = draw.font
+    stampable = type(font) is _MemoFont and font is _font  # the memoising default font, not ImageDraw.font's
+    red = draw.draw.draw_ink(_PILColor.getcolor("red", "RGB"))
+    for box, text in zip(boxes, texts):
+        # the rectangle: Pillow's argument checks pass for four plain numbers in order, and then the recorder's
+        # outline is all that happens
+        c = None
+        if (image._im is None and type(box) in (list, tuple) and len(box) == 4
+                and all(type(v) is float or type(v) is int for v in box) and box[0] <= box[2] and box[1] <= box[3]):
+            c = _ints(box, 4)
+        if c is None:
+            draw.rectangle(box, outline="red", width=3)
+        else:
+            _outline(lst, c[0], c[1], c[2], c[3], red, 3)
+        x, y = box[0] + 5, box[1] + 5
+        key = None
+        if (stampable and image._im is None and type(text) is str and type(x) is float and type(y) is float
+                and 0 <= x < _COORD_MAX and 0 <= y < _COORD_MAX):  # (a NaN fails the comparisons)
+            fx, fy = math.modf(x)[0], math.modf(y)[0]
+            cx, cy = start_class(fx, _UPPER_X), start_class(fy, _UPPER_Y)
+            if cx is not None and cy is not None:
+                key = (text, cx, cy)
+        if key is None or key in _stamp_never:
+            stamp_stats["fallbacks"] += 1
+            draw.text(xy=(x, y), text=text, **_TEXT)
+            continue
+        stamp = _stamps.get(key)
+        if stamp is not None and _replay(lst, font, stamp, int(x), int(y), (fx, fy), cx, cy):
+            stamp_stats["hits"] += 1
+            continue
+        got = _capture_text(draw, x, y, fx, fy, text)
+        stamp_stats["captures"] += 1
+        with _stamp_lock:
+            first = _stamp_first.get(key)
+            if got is None or stamp is not None or (first is not None and first[1] != got):
+                # not a stamp, a trusted stamp the font no longer agrees with, or two captures that differ
+                _stamp_never.add(key)
+                _stamps.pop(key, None)
+                _stamp_first.pop(key, None)
+            elif first is None:
+                _stamp_first[key] = ((fx, fy), got)
+            elif first[0] != (fx, fy):  # a second fraction of the class gave the same stamp
+                _stamps[key] = got
+                del _stamp_first[key]
 
 
 _lib_ok = None

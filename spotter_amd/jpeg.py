@@ -31,9 +31,9 @@ import types
 import numpy as np
 import torch
 
-from ._lib import (SP_JPEG_BATCH_MAX, SP_JPEG_NOT_ELIGIBLE, SP_JPEG_PKG_SMALL, SP_JPEG_UNSUPPORTED, SpJpegBatchItem,
-                   SpJpegBatchTotals, SpJpegEncBatchItem, SpJpegEncBatchTotals, SpJpegEncLayout, SpJpegEntropyItem,
-                   SpJpegEntropyTotals, SpJpegLayout, SpJpegScan, lib)
+from ._lib import (SP_DRAW_BATCH_MAX, SP_JPEG_BATCH_MAX, SP_JPEG_NOT_ELIGIBLE, SP_JPEG_PKG_SMALL, SP_JPEG_UNSUPPORTED,
+                   SpDrawBatchItem, SpJpegBatchItem, SpJpegBatchTotals, SpJpegEncBatchItem, SpJpegEncBatchTotals,
+                   SpJpegEncLayout, SpJpegEntropyItem, SpJpegEntropyTotals, SpJpegLayout, SpJpegScan, lib)
 from .config import check_jpeg_entropy, jpeg_entropy_from_env
 
 
@@ -786,8 +786,8 @@ class JpegEncoder:
     def encode_many(self, srcs, quality=-1, subsampling=-1, comments=None, max_workers=None) -> list:
         """encode() over a list of sources at one quality / subsampling: one file per source, byte for byte what
         encode(src, quality, subsampling, comment) returns. srcs: uint8 [H, W, 3 | 4] device tensors (encode()'s stride
-        rules), DeviceRGBImages (pending draws are flushed first) and PIL RGB images, mixed freely; comments: None, or
-        one bytes / None per source.
+        rules), DeviceRGBImages (their pending draws are applied first, all of them together: flush_many) and PIL RGB
+        images, mixed freely; comments: None, or one bytes / None per source.
 
         Per chunk (up to SP_JPEG_BATCH_MAX images, closed earlier where its workspace, packed bit capacity or staged
         host pixels would pass KEEP_ENC_WORK / KEEP_ENC_BITS / KEEP_ENC_PIX; a single image beyond one of them goes
@@ -804,6 +804,8 @@ class JpegEncoder:
         if workers < 1:
             raise ValueError("max_workers must be at least 1")
         self.stats["calls"] += 1
+        # the pending draws of the whole call in one launch per SP_DRAW_BATCH_MAX images, not one per image in _source
+        flush_many([s for s in srcs if isinstance(s, DeviceRGBImage) and s._im is None])
         descs = [self._source(s, quality, subsampling) for s in srcs]
         caps = (KEEP_ENC_WORK, KEEP_ENC_BITS, KEEP_ENC_PIX)
         out = []
@@ -961,12 +963,18 @@ class DeviceRGBImage(_PILImage.Image):
         lst = self._draw_list
         if not len(lst):
             return
+        t = self._drawable()
+        _draw_stage(t.device).run(lst, t)
+        lst.clear()
+
+    def _drawable(self) -> torch.Tensor:
+        """The tensor a draw may write in place: the image's own packed-RGB tensor, or a clone of a shared or
+        differently laid out one, which the image owns from here on."""
         t = self._dev
         if not self._owns or t.stride(2) != 1 or t.stride(1) != 3 or t.stride(0) < 3 * t.shape[1]:
             t = self._dev = t.clone(memory_format=torch.contiguous_format)  # device to device
             self._owns = True
-        _draw_stage(t.device).run(lst, t)
-        lst.clear()
+        return t
 
     def _lazy_copy(self):
         t = self.spotter_device_rgb  # pending draws are applied first (by the owner in place, else to a clone)
@@ -1021,6 +1029,77 @@ class _DrawStage:
         self._stage = self._table = None
         self._copied = None  # event: the last H2D copy out of the pinned buffer is done
         self._done = None    # event: the last launch is done with the device table
+        # run_many's counters: launches, images in them, bytes uploaded, host waits for an event that had not passed
+        self.stats = {"batch_launches": 0, "batch_images": 0, "batch_h2d_bytes": 0, "batch_waits": 0}
+
+    def _wait(self, event):
+        if event is not None and not event.query():
+            self.stats["batch_waits"] += 1
+            event.synchronize()
+
+    def _alloc(self, n):
+        """New staging of at least n bytes: (pinned host buffer, device buffer)."""
+        return _grow(None, n, torch.uint8), _grow(None, n, torch.uint8, self.dev)
+
+    def pack_batch(self, pairs):
+        """The batch buffer of run_many in the pinned staging buffer (lock held, the buffer free):
+        [each list's packed table, as sp_draw_pack writes it, back to back at multiples of 16][the sp_draw_batch_item
+        rows, planned]. Returns (rows, the buffer as a uint8 array over the staging buffer, the rows' offset)."""
+        L = lib()
+        items = (SpDrawBatchItem * len(pairs))()
+        rows = C.sizeof(items)
+
+        def pack_all():
+            cap = 0 if self._stage is None else self._stage.numel()
+            base = self._stage.data_ptr() if cap else 0
+            off, fits = 0, True
+            for it, (lst, _) in zip(items, pairs):
+                room = cap - rows - off
+                need = lst.pack(base + off, room) if fits and room > 0 else lst.pack()
+                fits = fits and need <= room
+                it.table_off, it.table_bytes = off, need  # (a table's size is a multiple of 16)
+                off += need
+            return off, fits
+
+        end, fits = pack_all()
+        if not fits:
+            self._wait(self._done)  # the old device table goes back to the caching allocator
+            self._stage, self._table = self._alloc(end + rows)
+            end, fits = pack_all()
+            assert fits
+        for it, (_, t) in zip(items, pairs):
+            it.rgb, it.height, it.width, it.row_stride = t.data_ptr(), t.shape[0], t.shape[1], t.stride(0)
+        hp = self._stage.data_ptr()
+        if L.sp_draw_batch_plan(items, len(pairs), hp, end) < 0:
+            raise RuntimeError(f"sp_draw_batch_plan: {L.sp_last_error().decode(errors='replace')}")
+        C.memmove(hp + end, items, rows)
+        return items, self._stage[:end + rows].numpy(), end
+
+    def run_many(self, pairs):
+        """The draw lists of up to SP_DRAW_BATCH_MAX images, pairs of (non-empty DrawList, its drawable tensor), in one
+        launch on the current stream: pack_batch's buffer, one H2D copy, one sp_draw_batch_rgb. The staging buffers
+        and their two events are run()'s, so single and batched flushes on any streams keep one order."""
+        with self._lock:
+            L = lib()
+            cur = torch.cuda.current_stream(self.dev)
+            self._wait(self._copied)  # the pinned buffer is free again
+            items, buf, end = self.pack_batch(pairs)
+            n, nbytes = len(pairs), len(buf)
+            hp, dp = self._stage.data_ptr(), self._table.data_ptr()
+            if self._done is not None:
+                cur.wait_event(self._done)  # another stream's previous launch may still read the device table
+            self._table[:nbytes].copy_(self._stage[:nbytes], non_blocking=True)
+            self._copied = torch.cuda.Event()
+            self._copied.record(cur)
+            rc = L.sp_draw_batch_rgb(dp + end, items, n, hp, dp, end, cur.cuda_stream)
+            if rc:
+                raise RuntimeError(f"sp_draw_batch_rgb: {L.sp_last_error().decode(errors='replace')}")
+            self._done = torch.cuda.Event()
+            self._done.record(cur)
+            st = self.stats
+            st["batch_launches"] += 1
+            st["batch_images"] += n
+            st["batch_h2d_bytes"] += nbytes
 
     def run(self, lst, rgb: torch.Tensor):
         with self._lock:
@@ -1060,6 +1139,30 @@ def _draw_stage(device) -> _DrawStage:
         if s is None:
             s = _stages[dev] = _DrawStage(dev)
         return s
+
+
+def flush_many(images) -> None:
+    """DeviceRGBImage.flush over any number of images of one device, on the current stream: the pending draw lists of
+    up to SP_DRAW_BATCH_MAX images go up in one copy and are applied by one sp_draw_batch_rgb launch (a group per
+    SP_DRAW_BATCH_MAX images with draws; a single image takes the same path). Images with nothing recorded are left
+    out and not touched; an image listed twice is flushed once. Per image the ownership rule is flush()'s (a shared
+    or not packed-RGB tensor is cloned first), and the pixels are flush()'s, bit for bit."""
+    todo, seen = [], set()
+    for im in images:
+        if len(im._draw_list) and id(im) not in seen:
+            seen.add(id(im))
+            todo.append(im)
+    if not todo:
+        return
+    dev = todo[0]._dev.device
+    if any(im._dev.device != dev for im in todo):
+        raise ValueError("flush_many: the images are on more than one device")
+    stage = _draw_stage(dev)
+    for i in range(0, len(todo), SP_DRAW_BATCH_MAX):
+        group = todo[i:i + SP_DRAW_BATCH_MAX]
+        stage.run_many([(im._draw_list, im._drawable()) for im in group])
+        for im in group:
+            im._draw_list.clear()
 
 
 _SUBSAMPLING = {-1: -1, 0: 0, 1: 1, 2: 2, "4:4:4": 0, "4:2:2": 1, "4:2:0": 2, "4:1:1": 2}
